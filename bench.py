@@ -9,6 +9,11 @@ their scalar reads). Inputs are synthetic and resident in HBM before the timed r
 ("Least-squares linear regression, dense 10M x 512 fp32, 256 chains on 1 MI355X"); per-GPU work
 is fixed as N grows (weak scaling: every GPU runs its own 256 chains x 10M rows).
 
+A plain run sets up, warms up, times the steps of that one workload, writes the last step's
+results if --dump-outputs is given, and prints its line. --full adds, after the headline, the CPU
+baselines, the secondary workloads (the other BASELINE configs, precisions and updaters), c5's
+store-mode probe and the detail file.
+
 Prints ONE JSON line (rank 0), kept under LINE_LIMIT bytes; the secondary workloads' full records
 go to --detail (a JSON file), their summary onto the line.
 """
@@ -56,6 +61,8 @@ DEFAULT_SECONDARY = ("c3:f32,c3:f64::f64,c3:f64,c2:f64,c1:f64,c4:f32,c4:f64,c4:f
 DEFAULT_SECONDARY_MULTI = "c3:f32,c3:f64::f64,c5:f32"
 SECONDARY_ROWS_MULTI = {"c5": 125_000_000}
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
+DEFAULT_DETAIL = os.path.join("bench_out", "bench_detail.json")   # --full's detail file
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs writes at most this much
 
 
 def pmc_traffic(workload, grad, variant, storage, rows, compute="f32", updater="simple"):
@@ -187,11 +194,21 @@ def parse():
                          "reference's default is 0.001; BASELINE's configs run 0)")
     ap.add_argument("--no-arena", action="store_true",
                     help="allocate each workload's rows separately (A/B of the one-allocation arena)")
-    ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
-                    help="file for the full secondary records ('' = none); stdout carries a summary")
+    ap.add_argument("--detail", default=None,
+                    help="file for the full headline and secondary records ('' = none; default: none in a "
+                         f"plain run, {DEFAULT_DETAIL} with --full); stdout carries a summary")
     ap.add_argument("--prewarm-s", type=float, default=1.0,
                     help="untimed epochs for this long before the warmup steps (GPU clock ramp)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure what a plain run leaves out: the CPU baselines, the "
+                         "secondary workloads (--secondary), c5's store-mode probe, and the detail file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step of the headline workload returned to its caller "
+                         "(the folded weights, the loss sum and the sample count) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.secondary and not args.full:
+        ap.error("--secondary workloads are measured only with --full")
+    return args
 
 
 class Arena:
@@ -392,9 +409,11 @@ def cpu_baseline_c1(budget_s, seed=42):
 
 def run_workload(torch, dist, pkg, dev, rank, world, local, workload, compute, rows, fraction,
                  steps, warmup, prewarm_s, features=0, chains=0, updater="", storage="", backend="nccl",
-                 skew=0, tol=0.0, arena=None):
+                 skew=0, tol=0.0, arena=None, store_probe=False, keep_outputs=False):
     """One workload: synthetic shard in HBM, prewarm, W warmup steps, K timed steps (barrier +
-    synchronize on both sides, max over ranks). Returns the measurement as a dict."""
+    synchronize on both sides, max over ranks). Returns the measurement as a dict. store_probe:
+    c5's store-mode probe (launches of its own) after the timed steps; keep_outputs: the last
+    timed step's results, copied to the host after the timed region, under "_outputs"."""
     import numpy as np
     # the ranks' scalar agreements (prewarm epoch count, elapsed time): device tensors over RCCL,
     # host tensors over gloo
@@ -615,7 +634,12 @@ def run_workload(torch, dist, pkg, dev, rank, world, local, workload, compute, r
         # per timed step, the chain kernel's ms (the detail file only; the stdout line drops it)
         "kernel_ms_series": [round(x, 4) for x in kernel_ms],
     }
-    if workload == "c5" and csr:
+    if keep_outputs:
+        # what the loop's caller holds after the last timed step: the folded weights and the
+        # step's loss sum and sample count (the three driver scalars' last two)
+        res["_outputs"] = {"weights": engine.to_host(w), "loss_sum": np.array([loss], np.float64),
+                           "count": np.array([cnt], np.float64)}
+    if store_probe and workload == "c5" and csr:
         res["c5_store_probe"] = c5_store_probe(torch, pkg, engine, params, w0, parts, all_parts, empty,
                                                rank, P, avg_kernel_s * 1e3)
     del engine, data, parts, all_parts
@@ -659,6 +683,20 @@ def c5_store_probe(torch, pkg, engine, params, w, parts, all_parts, empty, rank,
             "mode": "fast" if marginal <= C5_FAST_NS[comp] else "slow"}
 
 
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: each array as path/<name>.npy in float64, `limit` bytes in all. An array
+    past its equal share of the limit is written as a fixed sample: its elements at sorted
+    indices drawn without replacement by a generator seeded with the array's length."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = (limit // max(len(arrays), 1) - 256) // 8   # (256: room for the .npy header)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if a.size > share:
+            a = a[np.sort(np.random.default_rng(a.size).choice(a.size, size=share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
@@ -696,9 +734,12 @@ def main():
     dev = torch.device("cuda", local)
     torch.cuda.set_device(dev)
 
-    spec_list = args.secondary if args.secondary is not None else \
+    # a plain run measures the headline workload alone; --full adds the secondaries, the CPU
+    # baselines, c5's store probe and the detail file
+    spec_list = "" if not args.full else args.secondary if args.secondary is not None else \
         (DEFAULT_SECONDARY if world == 1 else DEFAULT_SECONDARY_MULTI)
     secondary = [s for s in spec_list.split(",") if s]
+    detail = args.detail if args.detail is not None else (DEFAULT_DETAIL if args.full else "")
     sec_rows = SECONDARY_ROWS if world == 1 else SECONDARY_ROWS_MULTI
 
     def rows_of(wl):
@@ -713,7 +754,10 @@ def main():
     res = run_workload(torch, dist, pkg, dev, rank, world, local, args.workload, args.compute,
                        args.rows, args.fraction, args.steps, args.warmup, args.prewarm_s, args.features,
                        args.chains, args.updater, args.storage, args.backend, args.skew_rows, args.tol,
-                       arena=arena)
+                       arena=arena, store_probe=args.full, keep_outputs=bool(args.dump_outputs))
+    outputs = res.pop("_outputs", None)
+    if outputs is not None and rank == 0:   # (the folded result is the same on every rank)
+        dump_outputs(args.dump_outputs, outputs)
     grad, d, P, step, csr, upd_name, reg = res.pop("_meta")
     res.pop("loss")
     series = res.pop("kernel_ms_series")
@@ -727,7 +771,7 @@ def main():
         **({"ranks": res["ranks"]} if "ranks" in res else {}),
         **({"c5_store_probe": res["c5_store_probe"]} if "c5_store_probe" in res else {}),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(grad, d, P, step, args.cpu_seconds,
                                            csr_nnz=CSR_NNZ[args.workload] if csr else 0,
                                            updater=upd_name, reg=reg)
@@ -745,7 +789,8 @@ def main():
         try:
             r = run_workload(torch, dist, pkg, dev, rank, world, local, wl, comp or "f32",
                              rows_of(wl), 1.0, args.steps, args.warmup,
-                             min(args.prewarm_s, 0.5), updater=upd, storage=sto, arena=arena)
+                             min(args.prewarm_s, 0.5), updater=upd, storage=sto, arena=arena,
+                             store_probe=True)
         except Exception as e:   # a secondary line never hides the headline
             records.append({"spec": spec, "error": f"{type(e).__name__}: {e}"})
             continue
@@ -755,8 +800,8 @@ def main():
         r["loss"] = float(r["loss"])
         records.append(r)
     if rank == 0:
-        if records or args.detail:
-            out["detail_file"] = write_detail(args.detail, dict(out, kernel_ms_series=series), records)
+        if records or detail:
+            out["detail_file"] = write_detail(detail, dict(out, kernel_ms_series=series), records)
         print(final_line(out, records), flush=True)
     if world > 1:
         dist.destroy_process_group()

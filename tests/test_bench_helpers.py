@@ -182,6 +182,42 @@ def test_bench_prints_its_line_last(monkeypatch, capsys, tmp_path):
     assert src.count("print(") == 1 and "final_line(" in src
 
 
+def test_plain_run_flags(monkeypatch):
+    """A plain run measures the headline alone: --full and --dump-outputs are off by default,
+    --steps sets the timed steps, and a secondary list without --full is refused, not ignored."""
+    import pytest
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.detail, a.steps, a.warmup) == (False, "", None, 7, 3)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--secondary=", "--no-cpu-baseline", "--dump-outputs", "d"])
+    assert bench.parse().dump_outputs == "d"
+    monkeypatch.setattr("sys.argv", ["bench.py", "--secondary", "c3:f32"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--secondary", "c3:f32"])
+    assert bench.parse().full
+
+
+def test_dump_outputs_writes_float64_arrays_within_the_limit(tmp_path):
+    """--dump-outputs: one float64 .npy per array, whole when it fits its share of the limit,
+    otherwise the same fixed sample on every call."""
+    import numpy as np
+    w = np.arange(5000, dtype=np.float64) * 0.5
+    arrays = {"weights": w, "loss_sum": np.array([3.25]), "count": np.array([7.0])}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["count.npy", "loss_sum.npy", "weights.npy"]
+    got = np.load(tmp_path / "a" / "weights.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, w)
+    assert np.load(tmp_path / "a" / "count.npy")[0] == 7.0
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), arrays, limit=3 * 1024)
+    s = np.load(tmp_path / "b" / "weights.npy")
+    assert s.size == (1024 - 256) // 8 and np.array_equal(s, np.load(tmp_path / "c" / "weights.npy"))
+    assert np.isin(s, w).all() and np.all(np.diff(s) > 0)
+    assert sum(p.stat().st_size for p in (tmp_path / "b").iterdir()) <= 3 * 1024
+    assert bench.DUMP_LIMIT_BYTES <= 64_000_000
+
+
 def test_arena_carves_aligned_views_and_resets():
     """The one-allocation arena of the synthetic shards (bench.Arena) hands out non-overlapping,
     4 KiB-aligned views of one buffer, refuses to overrun it, and is reused after reset()."""

@@ -459,7 +459,7 @@ def test_bench_two_ranks_gloo():
     fold -- run with two ranks sharing cuda:0 over gloo (RCCL refuses two ranks on one device;
     the driver's 8-GPU node runs the nccl form). The line reports both ranks' samples."""
     import json
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full",
            "--rows", "200000", "--secondary", "c3:f32,c5:f32", "--secondary-rows", "100000",
            "--steps", "3", "--warmup", "1", "--prewarm-s", "0.2"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)

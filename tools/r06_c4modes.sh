@@ -21,7 +21,7 @@ print(json.dumps({c: {"dispatches": len(v), "mean": statistics.mean(v.values()),
 PY
 done
 T0=$(date +%s.%N)
-timeout -k 10 500 python3 bench.py --workload c2 --secondary c5:f32 --secondary-rows 125000000 --no-cpu-baseline --steps 20 --warmup 5 --detail $O/c5full_detail.json > $O/c5full.json 2> $O/c5full.err || { tail -5 $O/c5full.err; exit 1; }
+timeout -k 10 500 python3 bench.py --full --workload c2 --secondary c5:f32 --secondary-rows 125000000 --no-cpu-baseline --steps 20 --warmup 5 --detail $O/c5full_detail.json > $O/c5full.json 2> $O/c5full.err || { tail -5 $O/c5full.err; exit 1; }
 T1=$(date +%s.%N)
 python3 -c "print('c5 full-shard bench process seconds:', $T1 - $T0)"
 tail -c 700 $O/c5full.json

@@ -5,5 +5,5 @@ rc=$?; tail -3 $O/pytest_gpu.log; echo "pytest rc=$rc"
 case $rc in 0|1) ;; *) exit $rc;; esac
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -5 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || exit 1
 tail -c 400 $O/bench.json
