@@ -180,6 +180,39 @@ int32_t psgd_convergence_terms_device(psgd_ctx* ctx, int32_t d, const double* d_
 int32_t psgd_initial_regval(psgd_ctx* ctx, const psgd_params* params, int32_t d, const double* w,
                             double* regval_out);
 
+/* Scoring at fixed weights (no reference counterpart in the optimizer; MLlib's users get it from
+ * LogisticRegressionModel / SVMModel / LinearRegressionModel.predict over the RDD): one streaming
+ * pass over every registered partition, fp64 arithmetic whatever the storage dtype.
+ *
+ * psgd_evaluate: the loss of weights w over every registered row, gradient.compute(x, y, w)._2
+ * summed (PSGD.scala:254 at constant w). The weights are d long (the partitions' number of
+ * features): the multinomial LogisticGradient is not scored (there is no num_classes argument; a
+ * host that holds (K - 1) * d weights must refuse the call itself, as the Python package does).
+ * out3 = {lossSum, (double)count, (double)nCorrect}: count is the number of registered rows,
+ * nCorrect the rows with (x . w > 0.0 ? 1.0 : 0.0) == label for Logistic and Hinge (MLlib's default
+ * thresholds, 0.5 on the sigmoid and 0.0 on the SVM margin) and 0 for LeastSquares.
+ * part_out (nullable) [n_parts * 2] = {lossSum_p, nCorrect_p} in partition-index order; an empty
+ * partition gives {0, 0}, a registry of empty partitions {0, 0, 0} and PSGD_OK.
+ * Sums are deterministic: fixed-size row tiles summed in a fixed order, a partition's tiles added
+ * in tile order, the partitions in partition-index order -- a partition's lossSum has the same
+ * bits from run to run and whatever else is registered.
+ * Errors: PSGD_EINVAL for a null ctx / w / out3 or an unknown gradient, PSGD_ESTATE when no
+ * partition is registered.
+ * The _device forms take device pointers and are enqueued on `stream` without host
+ * synchronisation. All four wait for registration copies in flight and order themselves against
+ * an epoch running on another stream; they leave the epoch state alone (psgd_ctx_last_kernel,
+ * psgd_ctx_chain_launches and the chain times are unchanged, and a sampled epoch's batch plays no
+ * part: every registered row is scored). */
+int32_t psgd_evaluate(psgd_ctx* ctx, int32_t gradient, const double* w, double* out3, double* part_out);
+int32_t psgd_evaluate_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double* d_out3,
+                             double* d_part_out, void* stream);
+
+/* The raw dot x_r . w (w is d long) of every row of registered partition `part`, in iterator
+ * order: margins[n_rows]. The caller applies its own threshold or link function. PSGD_ESTATE for
+ * a partition that is not registered; an empty partition writes nothing. */
+int32_t psgd_predict(psgd_ctx* ctx, int64_t part, const double* w, double* margins);
+int32_t psgd_predict_device(psgd_ctx* ctx, int64_t part, const double* d_w, double* d_margins, void* stream);
+
 /* Diagnostics: which chain kernel the last epoch launched (DESIGN.md §3 has the table):
  * 100 + NV   per-sample dense chain (chain_dense), NV 16-byte row vectors per lane;
  * 200 / 201  general dense / CSR chain (chain_general);

@@ -13,14 +13,14 @@ from ._native import (DeviceError, IllegalArgumentException, UnsupportedOperatio
 from .data import (CsrPartition, DensePartition, DeviceCsrPartition, DevicePartition, PartitionedData,
                    shard_range)
 from .gradient import Gradient, HingeGradient, LeastSquaresGradient, LogisticGradient
-from .optimization import (DriverCheckpoint, HipEngine, ParallelizedSGD, ShardedEngine, make_params,
-                           runParallelizedSGD)
+from .optimization import (DriverCheckpoint, Evaluation, HipEngine, ParallelizedSGD, ShardedEngine, evaluate,
+                           make_params, runParallelizedSGD)
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .util import loadLibSVMFile
 
 __all__ = [
-    "ParallelizedSGD", "runParallelizedSGD", "HipEngine", "ShardedEngine", "make_params",
+    "ParallelizedSGD", "runParallelizedSGD", "evaluate", "Evaluation", "HipEngine", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",
     "SGDUpdater", "SimpleSGDUpdater", "SquaredL2SGDUpdater", "L1SGDUpdater",
     "AdaGradSGDUpdater", "AdamSGDUpdater",

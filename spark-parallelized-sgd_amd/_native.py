@@ -28,6 +28,7 @@ EXPORTED = (
     "psgd_ctx_last_kernel", "psgd_ctx_last_chain_ms", "psgd_ctx_chain_launches", "psgd_ctx_chain_ms",
     "psgd_vmm_stats", "psgd_reroll_stats", "psgd_libsvm_read", "psgd_libsvm_free",
     "psgd_sample_partition", "psgd_host_alloc", "psgd_host_free", "psgd_register_wait",
+    "psgd_evaluate", "psgd_evaluate_device", "psgd_predict", "psgd_predict_device",
 )
 
 
@@ -117,6 +118,10 @@ def lib():
             "psgd_host_alloc": ([vp, C.c_int64, C.POINTER(vp)], C.c_int32),
             "psgd_host_free": ([vp, vp], C.c_int32),
             "psgd_register_wait": ([vp], C.c_int32),
+            "psgd_evaluate": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_evaluate_device": ([vp, C.c_int32, vp, vp, vp, vp], C.c_int32),
+            "psgd_predict": ([vp, C.c_int64, vp, vp], C.c_int32),
+            "psgd_predict_device": ([vp, C.c_int64, vp, vp, vp], C.c_int32),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -319,3 +324,31 @@ class Context:
                                      w_out.ctypes.data, C.byref(rv), C.byref(loss), C.byref(cnt),
                                      counts.ctypes.data))
         return w_out, rv.value, loss.value, cnt.value, counts[:nparts]
+
+    # scoring at fixed weights -----------------------------------------------------------------
+    def evaluate(self, gradient: int, w):
+        """Host-pointer form (psgd_evaluate): (lossSum, count, nCorrect, partLoss, partCorrect)
+        of host weights w over every registered partition."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        nparts, _ = self.num_partitions()
+        out3 = np.zeros(3, dtype=np.float64)
+        part = np.zeros((max(nparts, 1), 2), dtype=np.float64)
+        check(self._L.psgd_evaluate(self.handle, int(gradient), w.ctypes.data, out3.ctypes.data,
+                                    part.ctypes.data))
+        return float(out3[0]), int(out3[1]), int(out3[2]), part[:nparts, 0].copy(), part[:nparts, 1].copy()
+
+    def evaluate_device(self, gradient: int, w_ptr, out3_ptr, part_ptr=None, stream=None):
+        """psgd_evaluate_device: enqueued on `stream`; out3[3] and part[n_parts * 2] on the device."""
+        check(self._L.psgd_evaluate_device(self.handle, int(gradient), w_ptr, out3_ptr, part_ptr, stream))
+
+    def predict(self, part: int, n_rows: int, w):
+        """Host-pointer form (psgd_predict): the dots x_r . w of partition `part`'s n_rows rows."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        out = np.zeros(int(n_rows), dtype=np.float64)
+        check(self._L.psgd_predict(self.handle, C.c_int64(part), w.ctypes.data, out.ctypes.data))
+        return out
+
+    def predict_device(self, part: int, w_ptr, margins_ptr, stream=None):
+        check(self._L.psgd_predict_device(self.handle, C.c_int64(part), w_ptr, margins_ptr, stream))

@@ -441,6 +441,11 @@ struct psgd_ctx {
     bool alpha_ok = false;
     // the fp64 CSR weight-vector size whose allocation failed (0: none): not retried
     size_t wf64_failed = 0;
+    // scoring at fixed weights (psgd_evaluate / psgd_predict): the partitions' tiling as uploaded
+    // with the descriptors, the tiles' partial sums [2 * tiles], the partitions' sums [2 * P], and
+    // the host-pointer forms' staging of w, out3 + part_out and a partition's margins
+    DevBuf eparts, etiles, epart, ew, emargins;
+    std::vector<psgd::EvalPart> eval_parts;
 };
 
 namespace {
@@ -615,6 +620,44 @@ int32_t scratch_release(psgd_ctx* ctx, hipStream_t st) {
     return PSGD_OK;
 }
 
+// Upload the registered partitions' descriptors when the registry has changed: the chains'
+// ChainDesc and, beside them, the scoring kernels' tiling (EvalPart, psgd_eval.hip) (ctx->mu held).
+int32_t upload_descs(psgd_ctx* ctx, hipStream_t st) {
+    if (!ctx->descs_dirty) return PSGD_OK;
+    const size_t P = ctx->parts.size();
+    HIP_TRY(ctx->descs.ensure(std::max<size_t>(P, 1) * sizeof(psgd::ChainDesc)));
+    HIP_TRY(ctx->eparts.ensure((P + 1) * sizeof(psgd::EvalPart)));
+    std::vector<psgd::ChainDesc> h;
+    std::vector<psgd::EvalPart> ep;
+    h.reserve(P);
+    ep.reserve(P + 1);
+    int64_t tiles = 0;
+    for (auto& kv : ctx->parts) {
+        const Part& q = kv.second;
+        psgd::ChainDesc c;
+        c.x = q.x;
+        c.y = q.y;
+        c.row_ptr = q.row_ptr;
+        c.col = q.col;
+        c.n_rows = q.n_rows;
+        c.ld = q.ld;
+        c.rows = nullptr;   // every row (sampled epochs get descriptors of their own)
+        h.push_back(c);
+        psgd::EvalPart e;
+        e.tile0 = tiles;
+        psgd::eval_geometry(q.layout, q.ld * (int64_t)dtype_size(q.dtype), q.max_nnz, &e.tile_rows, &e.group);
+        tiles += (q.n_rows + e.tile_rows - 1) / e.tile_rows;
+        ep.push_back(e);
+    }
+    ep.push_back(psgd::EvalPart{tiles, 1, 64});
+    if (P) HIP_TRY(hipMemcpyAsync(ctx->descs.p, h.data(), P * sizeof(psgd::ChainDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->eparts.p, ep.data(), ep.size() * sizeof(psgd::EvalPart), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ctx->eval_parts = ep;
+    ctx->descs_dirty = false;
+    return PSGD_OK;
+}
+
 // Allocate per-chain buffers and upload descriptors (ctx->mu held).
 int32_t prepare(psgd_ctx* ctx, int32_t d, int state_vectors, hipStream_t st) {
     const size_t P = ctx->parts.size();
@@ -645,27 +688,9 @@ int32_t prepare(psgd_ctx* ctx, int32_t d, int state_vectors, hipStream_t st) {
     if (state_vectors > 0)
         HIP_TRY(ctx->state.ensure(std::max<size_t>(P, 1) * (size_t)state_vectors *
                                   (size_t)std::max(d, 1) * sizeof(double)));
-    if (ctx->descs_dirty) {
-        std::vector<psgd::ChainDesc> h;
-        h.reserve(P);
-        for (auto& kv : ctx->parts) {
-            const Part& q = kv.second;
-            psgd::ChainDesc c;
-            c.x = q.x;
-            c.y = q.y;
-            c.row_ptr = q.row_ptr;
-            c.col = q.col;
-            c.n_rows = q.n_rows;
-            c.ld = q.ld;
-            c.rows = nullptr;   // every row (sampled epochs get descriptors of their own)
-            h.push_back(c);
-        }
-        if (P) {
-            HIP_TRY(hipMemcpyAsync(ctx->descs.p, h.data(), P * sizeof(psgd::ChainDesc),
-                                   hipMemcpyHostToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        ctx->descs_dirty = false;
+    {
+        const int32_t rc = upload_descs(ctx, st);
+        if (rc) return rc;
     }
     return PSGD_OK;
 }
@@ -767,6 +792,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
         for (DevBuf* b : {&ctx->descs, &ctx->w_in, &ctx->w_out, &ctx->state, &ctx->rv, &ctx->loss,
                           &ctx->cnt_d, &ctx->cnt, &ctx->steps, &ctx->partial, &ctx->tmp, &ctx->zbuf, &ctx->wf32, &ctx->stamps, &ctx->walpha, &ctx->wnsq0,
                           &ctx->sdescs, &ctx->srows, &ctx->sys, &ctx->xstate,
+                          &ctx->eparts, &ctx->etiles, &ctx->epart, &ctx->ew, &ctx->emargins,
                           &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
@@ -1500,6 +1526,152 @@ int32_t psgd_initial_regval(psgd_ctx* ctx, const psgd_params* params, int32_t d,
     } else {
         *regval_out = h[1] * params->reg_param;  // UPD.scala:147 with shrinkage 0
     }
+    return PSGD_OK;
+}
+
+// ---- Scoring at fixed weights (kernels in psgd_eval.hip) ----
+// The calls share the context with the epochs but none of their state: they read the base
+// descriptors (never an epoch's sampled ones), use scratch of their own, and leave the watchdog
+// flags, last_variant, the chain-launch counter and its events, and the CSR weight-vector sets alone.
+
+// What an epoch does before it reads the partitions (prepare): order `st` after the newest work on
+// the context's scratch, wait for registration copies in flight, upload the descriptors (ctx->mu held).
+static int32_t score_prepare(psgd_ctx* ctx, hipStream_t st) {
+    int32_t rc = scratch_acquire(ctx, st);
+    if (rc) return rc;
+    if (ctx->copies_pending) {
+        HIP_TRY(hipEventRecord(ctx->copy_ev, ctx->copy_stream));
+        HIP_TRY(hipStreamWaitEvent(st, ctx->copy_ev, 0));
+        ctx->copies_pending = false;
+    }
+    return upload_descs(ctx, st);
+}
+
+// Partitions [p0, p0 + n) of the registry in index order (n = all of them for an evaluation, one
+// for a prediction) scored at d_w on `st` (ctx->mu held, score_prepare done).
+static int32_t score_enqueue(psgd_ctx* ctx, int32_t gradient, size_t p0, size_t n, const double* d_w,
+                             double* d_out3, double* d_part_out, double* d_margins, hipStream_t st) {
+    const Part& first = ctx->parts.begin()->second;
+    const std::vector<psgd::EvalPart>& ep = ctx->eval_parts;
+    const int64_t n_items = ep[p0 + n].tile0 - ep[p0].tile0;
+    HIP_TRY(ctx->etiles.ensure((size_t)std::max<int64_t>(n_items, 1) * 2 * sizeof(double)));
+    HIP_TRY(ctx->epart.ensure(n * 2 * sizeof(double)));
+    double* tile_loss = ctx->etiles.as<double>();
+    double* tile_ok = tile_loss + std::max<int64_t>(n_items, 1);
+    const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>() + p0;
+    const psgd::EvalPart* d_ep = ctx->eparts.as<psgd::EvalPart>() + p0;
+    int e = psgd::launch_score(descs, d_ep, (int)n, n_items, first.layout, first.dtype == PSGD_F32 ? 1 : 0,
+                               gradient, d_w, first.d, tile_loss, tile_ok, d_margins, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("scoring kernel launch failed: ") + hipGetErrorString((hipError_t)e));
+    if (d_margins) return PSGD_OK;
+    e = psgd::launch_eval_reduce(descs, d_ep, (int)n, tile_loss, tile_ok, ctx->epart.as<double>(), d_part_out,
+                                 d_out3, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("scoring reduction launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+struct ScoreScratchGuard {
+    psgd_ctx* ctx;
+    hipStream_t st;
+    ~ScoreScratchGuard() { (void)scratch_release(ctx, st); }
+};
+
+int32_t psgd_evaluate_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double* d_out3,
+                             double* d_part_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (gradient < PSGD_GRADIENT_LOGISTIC || gradient > PSGD_GRADIENT_HINGE)
+        return fail(PSGD_EINVAL, "unknown gradient kind " + std::to_string(gradient));
+    if (!d_w || !d_out3) return fail(PSGD_EINVAL, "d_w/d_out3 are null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int32_t rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    return score_enqueue(ctx, gradient, 0, ctx->parts.size(), d_w, d_out3, d_part_out, nullptr, st);
+}
+
+int32_t psgd_evaluate(psgd_ctx* ctx, int32_t gradient, const double* w, double* out3, double* part_out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (gradient < PSGD_GRADIENT_LOGISTIC || gradient > PSGD_GRADIENT_HINGE)
+        return fail(PSGD_EINVAL, "unknown gradient kind " + std::to_string(gradient));
+    if (!w || !out3) return fail(PSGD_EINVAL, "w/out3 are null");
+    size_t P = 0, d = 0;
+    double *d_w = nullptr, *d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        P = ctx->parts.size();
+        d = (size_t)ctx->parts.begin()->second.d;
+        DeviceGuard g(ctx->device);
+        // (the staging buffers are scratch too: a scoring call on another stream may still read them)
+        int32_t rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->ew.ensure((d + 3 + 2 * P) * sizeof(double)));
+        d_w = ctx->ew.as<double>();
+        d_out = d_w + d;
+        HIP_TRY(hipMemcpyAsync(d_w, w, d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    int32_t rc = psgd_evaluate_device(ctx, gradient, d_w, d_out, d_out + 3, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    std::vector<double> h(3 + 2 * P);
+    HIP_TRY(hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(out3, h.data(), 3 * sizeof(double));
+    if (part_out) std::memcpy(part_out, h.data() + 3, 2 * P * sizeof(double));
+    return PSGD_OK;
+}
+
+int32_t psgd_predict_device(psgd_ctx* ctx, int64_t part, const double* d_w, double* d_margins, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_w) return fail(PSGD_EINVAL, "d_w is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const auto it = ctx->parts.find(part);
+    if (it == ctx->parts.end()) return fail(PSGD_ESTATE, "partition " + std::to_string(part) + " is not registered");
+    if (it->second.n_rows == 0) return PSGD_OK;
+    if (!d_margins) return fail(PSGD_EINVAL, "d_margins is null");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int32_t rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const size_t p0 = (size_t)std::distance(ctx->parts.begin(), it);
+    // (the dot needs no loss: LeastSquares' is the cheapest to throw away)
+    return score_enqueue(ctx, PSGD_GRADIENT_LEAST_SQUARES, p0, 1, d_w, nullptr, nullptr, d_margins, st);
+}
+
+int32_t psgd_predict(psgd_ctx* ctx, int64_t part, const double* w, double* margins) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!w) return fail(PSGD_EINVAL, "w is null");
+    size_t d = 0, n = 0;
+    double *d_w = nullptr, *d_m = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        const auto it = ctx->parts.find(part);
+        if (it == ctx->parts.end())
+            return fail(PSGD_ESTATE, "partition " + std::to_string(part) + " is not registered");
+        n = (size_t)it->second.n_rows;
+        if (n == 0) return PSGD_OK;
+        if (!margins) return fail(PSGD_EINVAL, "margins is null");
+        d = (size_t)it->second.d;
+        DeviceGuard g(ctx->device);
+        int32_t rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->ew.ensure((d + 3) * sizeof(double)));
+        HIP_TRY(ctx->emargins.ensure(n * sizeof(double)));
+        d_w = ctx->ew.as<double>();
+        d_m = ctx->emargins.as<double>();
+        HIP_TRY(hipMemcpyAsync(d_w, w, d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    int32_t rc = psgd_predict_device(ctx, part, d_w, d_m, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(margins, d_m, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PSGD_OK;
 }
 

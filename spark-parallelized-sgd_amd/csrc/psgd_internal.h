@@ -167,4 +167,28 @@ int launch_multinomial_chains(const ChainLaunch& L, const KParams& kp, int layou
 int launch_sample(const ChainDesc* base, ChainDesc* out, const uint64_t* xs_state, double fraction,
                   int32_t* rows, double* ys, int64_t stride, int n_chains, hipStream_t stream);
 
+// ---- Scoring at fixed weights (psgd_eval.hip: psgd_evaluate / psgd_predict) ----
+// The scoring kernels' view of a registered partition, beside its ChainDesc: its rows are cut into
+// tiles of tile_rows rows, numbered from tile0 on across the partitions in partition-index order
+// (entry n_parts closes the list: its tile0 is the number of tiles); a row is read by `group` lanes.
+struct EvalPart {
+    int64_t tile0;
+    int32_t tile_rows;
+    int32_t group;
+};
+// A partition's tile_rows and group from its own shape alone (dense: the row pitch in bytes; CSR:
+// its longest row), so that its sums do not depend on what else is registered.
+void eval_geometry(int layout, int64_t row_bytes, int64_t max_nnz, int32_t* tile_rows, int32_t* group);
+// Scores the n_items tiles of partitions descs[0 .. n_parts) (ep[0 .. n_parts]) at weights w[d]:
+// tile_loss / tile_ok [n_items] receive each tile's loss sum and correct predictions (Logistic,
+// Hinge: (dot > 0 ? 1 : 0) == label; LeastSquares: 0); margins (nullable; one partition only)
+// [n_rows] every row's dot. storage: 0 = f64, 1 = f32. -2: unknown gradient.
+int launch_score(const ChainDesc* descs, const EvalPart* ep, int n_parts, int64_t n_items, int layout,
+                 int storage, int gradient, const double* w, int d, double* tile_loss, double* tile_ok,
+                 double* margins, int num_cus, hipStream_t st);
+// part[2 p] / part[2 p + 1] (and part_out, nullable) = partition p's tiles added in tile order;
+// out3 = {lossSum, count, nCorrect}, the partitions added in partition-index order.
+int launch_eval_reduce(const ChainDesc* descs, const EvalPart* ep, int n_parts, const double* tile_loss,
+                       const double* tile_ok, double* part, double* part_out, double* out3, hipStream_t st);
+
 }  // namespace psgd

@@ -8,7 +8,8 @@
 // usage: psgd_run <file.libsvm> [--partitions P] [--features D] [--gradient logistic|
 //        least_squares|hinge] [--updater simple|squared_l2|l1|adagrad|adam] [--step S]
 //        [--iterations N] [--reg R] [--fraction F] [--tol T] [--compute f64|f32] [--device K]
-//        [--checkpoint FILE]
+//        [--checkpoint FILE] [--evaluate]
+// --evaluate prints a second line: lossSum, count, nCorrect and objective at the final weights.
 #include "../../include/psgd.h"
 
 #include <chrono>
@@ -143,6 +144,7 @@ int main(int argc, char** argv) {
     static const char* const kDt[] = {"f64", "f32"};
     int parts = 2, features = -1, device = 0, iterations = 100;
     std::string checkpoint;
+    bool evaluate = false;
     psgd_params p{};
     p.gradient = PSGD_GRADIENT_LOGISTIC;
     p.updater = PSGD_UPDATER_SIMPLE;
@@ -155,8 +157,14 @@ int main(int argc, char** argv) {
     p.adam_gamma = 0.999;
     p.adam_eps = 1e-8;
     p.num_classes = 2;
-    for (int a = 2; a + 1 < argc; a += 2) {
+    for (int a = 2; a < argc; a += 2) {
         const std::string k = argv[a];
+        if (k == "--evaluate") {   // a flag: no value follows
+            evaluate = true;
+            --a;
+            continue;
+        }
+        if (a + 1 >= argc) break;
         const char* v = argv[a + 1];
         if (k == "--partitions") parts = std::atoi(v);
         else if (k == "--features") features = std::atoi(v);
@@ -264,6 +272,16 @@ int main(int argc, char** argv) {
     print_array("chain_counts", counts_log.data(), counts_log.size());
     std::printf("\"partitions\": %d, \"rows\": %lld, \"d\": %d, \"epoch_seconds\": %.6f}\n",
                 data->n_parts, (long long)data->n_rows, d, epoch_s);
+    if (evaluate) {
+        // the final weights scored over every row (psgd_evaluate): objective = lossSum / count +
+        // updater.compute(w, 0, 0, 1, regParam)._2, the regVal of PSGD.scala:231-233 at those weights
+        double out3[3] = {0.0, 0.0, 0.0}, regVal = 0.0;
+        if (data->n_parts > 0) CHECK(psgd_evaluate(ctx, p.gradient, weights.data(), out3, nullptr));
+        CHECK(psgd_initial_regval(ctx, &p, d, weights.data(), &regVal));
+        std::printf("{\"evaluate\": {\"lossSum\": %.17g, \"count\": %lld, \"nCorrect\": %lld, \"objective\": %.17g}}\n",
+                    out3[0], (long long)out3[1], (long long)out3[2],
+                    out3[1] > 0.0 ? out3[0] / out3[1] + regVal : std::nan(""));
+    }
     CHECK(psgd_ctx_destroy(ctx));
     psgd_libsvm_free(data);
     return 0;

@@ -29,7 +29,8 @@ import numpy as np
 from . import _native as N
 from .data import (CsrPartition, DensePartition, DeviceCsrPartition, DevicePartition, PartitionedData,
                    shard_range)
-from .gradient import Gradient, LogisticGradient, gradient_kind, num_classes, weight_dim
+from .gradient import (Gradient, LeastSquaresGradient, LogisticGradient, gradient_kind, num_classes,
+                       weight_dim)
 from .updater import AdamSGDUpdater, SGDUpdater, updater_kind
 
 log = logging.getLogger("org.apache.spark.mllib.optimization.ParallelizedSGD")
@@ -379,6 +380,161 @@ class HipEngine(ShardedEngine):
         with self.torch.cuda.stream(self.stream):
             return w_dev.detach().cpu().numpy().astype(np.float64)
 
+    # scoring at fixed weights (psgd_evaluate_device / psgd_predict_device) ----------------------
+    def _score_weights(self, w):
+        """w (host array or device tensor) as a contiguous f64 tensor on the engine's device, one
+        entry per feature (self.stream is current)."""
+        nf = self._data.num_features
+        if self.torch.is_tensor(w):
+            w_dev = w.detach().to(device=self.dev, dtype=self.torch.float64).contiguous()
+        else:
+            w_dev = self.torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.dev)
+        if w_dev.dim() != 1 or w_dev.shape[0] != nf:
+            raise IllegalArgumentException(
+                f"requirement failed: BLAS.dot(x: Vector, y: Vector) was given Vectors with "
+                f"non-matching sizes: x.size = {nf}, y.size = {w_dev.numel()}")
+        return w_dev
+
+    def evaluate(self, gradient, w) -> "EngineScore":
+        """lossSum (gradient.compute(x, y, w)._2 summed), count and nCorrect of weights w over every
+        partition of the data, on all ranks, with the per-partition sums (psgd_evaluate_device: one
+        streaming fp64 pass, deterministic sums). w: a host array or a device tensor of
+        num_features doubles. With several ranks each scores its own partitions; the ranks
+        all-gather their three sums and per-partition pairs (the backends of exchange()) and add
+        lossSum in rank order, which is partition order (the blocks are contiguous); a rank without
+        partitions contributes zeros. Every registered row counts, whatever an earlier epoch sampled."""
+        if num_classes(gradient) > 2:
+            raise N.UnsupportedOperationException(
+                "evaluate with the multinomial LogisticGradient (numClasses > 2) is not built")
+        kind = gradient_kind(gradient)
+        torch = self.torch
+        P = self._data.num_partitions
+        shards = [shard_range(P, r, self.world) for r in range(self.world)]
+        width = 3 + 2 * max(max(hi - lo for lo, hi in shards), 1)
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            w_dev = self._score_weights(w)
+            buf = torch.zeros(width, dtype=torch.float64, device=self.dev)
+            if self.n_local > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    self.ctx.evaluate_device(kind, w_dev.data_ptr(), buf.data_ptr(), buf.data_ptr() + 24,
+                                             self.stream.cuda_stream)
+            if self.world > 1:
+                import torch.distributed as dist
+                out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
+                if dist.get_backend() == "gloo":
+                    dist.all_gather(list(out.view(self.world, width).unbind(0)), buf)
+                else:
+                    dist.all_gather_into_tensor(out, buf)
+                h = out.cpu().numpy().reshape(self.world, width)
+            else:
+                h = buf.cpu().numpy().reshape(1, width)
+        loss_sum, count, correct = 0.0, 0, 0
+        part_loss, part_correct = np.zeros(P), np.zeros(P, dtype=np.int64)
+        for r, (lo, hi) in enumerate(shards):   # rank order = partition order
+            loss_sum = loss_sum + float(h[r, 0])
+            count += int(h[r, 1])
+            correct += int(h[r, 2])
+            pairs = h[r, 3: 3 + 2 * (hi - lo)].reshape(hi - lo, 2)
+            part_loss[lo:hi] = pairs[:, 0]
+            part_correct[lo:hi] = pairs[:, 1].astype(np.int64)
+        return EngineScore(loss_sum, count, correct, part_loss, part_correct)
+
+    def predict(self, p: int, w):
+        """The raw dots x_r . w of local partition p's rows, in iterator order, as a device tensor
+        (psgd_predict_device); the caller applies its own threshold or link function."""
+        if not (self.lo <= p < self.hi):
+            raise IllegalArgumentException(
+                f"requirement failed: partition {p} is not held by rank {self.rank} "
+                f"(its partitions are [{self.lo}, {self.hi}))")
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            w_dev = self._score_weights(w)
+            n = self._data.partitions[p].n_rows
+            out = torch.empty(n, dtype=torch.float64, device=self.dev)
+            with self.ctx.engine_lock:
+                if self.ctx.registered_token != self._key:
+                    self._register(self._data)
+                self.ctx.predict_device(p, w_dev.data_ptr(), out.data_ptr(), self.stream.cuda_stream)
+            keep = torch.cuda.Event()
+            keep.record(self.stream)
+        caller.wait_stream(self.stream)
+        out.record_stream(caller)
+        keep.synchronize()   # w_dev may be a temporary of this call
+        return out
+
+
+EngineScore = collections.namedtuple("EngineScore", "lossSum count nCorrect partLoss partCorrect")
+
+
+class Evaluation:
+    """A model scored on a data set: lossSum and count over every row, meanLoss = lossSum / count,
+    regVal = updater.compute(w, 0, 0, 1, regParam)._2 (the reference's own definition,
+    ParallelizedSGD.scala:231-233), objective = meanLoss + regVal, accuracy = nCorrect / count at
+    MLlib's default thresholds (None for LeastSquaresGradient), and the per-partition partLoss /
+    partCorrect. With count == 0, meanLoss and objective are NaN and accuracy is None."""
+
+    def __init__(self, lossSum: float, count: int, nCorrect: Optional[int], regVal: float,
+                 partLoss=(), partCorrect=()):
+        self.lossSum = float(lossSum)
+        self.count = int(count)
+        self.nCorrect = None if nCorrect is None else int(nCorrect)
+        self.regVal = float(regVal)
+        self.partLoss = np.asarray(partLoss, dtype=np.float64)
+        self.partCorrect = np.asarray(partCorrect, dtype=np.int64)
+
+    @property
+    def meanLoss(self) -> float:
+        return self.lossSum / self.count if self.count > 0 else float("nan")
+
+    @property
+    def objective(self) -> float:
+        return self.meanLoss + self.regVal
+
+    @property
+    def accuracy(self) -> Optional[float]:
+        if self.nCorrect is None or self.count == 0:
+            return None
+        return self.nCorrect / self.count
+
+    def __repr__(self) -> str:
+        return (f"Evaluation(lossSum={self.lossSum!r}, count={self.count}, meanLoss={self.meanLoss!r}, "
+                f"regVal={self.regVal!r}, objective={self.objective!r}, accuracy={self.accuracy!r})")
+
+
+def evaluate(data: PartitionedData, gradient: Gradient, updater: SGDUpdater, regParam: float, weights,
+             *, engine=None) -> Evaluation:
+    """Score `weights` (a host array or a device tensor of num_features doubles) on `data`: the
+    true loss and objective at those weights -- not the training's running chain loss -- and the
+    accuracy of the classifiers (Evaluation).
+
+    The engine reuses the device context's registration when it holds this data already, so
+    scoring the training set after training copies nothing. Scoring another PartitionedData (a
+    held-out set) registers it in the training set's place, as any second engine on the device
+    does; training on the first set afterwards registers that one again. The multinomial
+    LogisticGradient (numClasses > 2) raises UnsupportedOperationException."""
+    if num_classes(gradient) > 2:
+        raise N.UnsupportedOperationException(
+            "evaluate with the multinomial LogisticGradient (numClasses > 2) is not built")
+    gradient_kind(gradient)
+    classifier = not isinstance(gradient, LeastSquaresGradient)
+    if data.num_partitions == 0:
+        return Evaluation(0.0, 0, 0 if classifier else None, float("nan"))
+    if engine is None:
+        rank, world, _ = _dist()
+        engine = HipEngine(data, rank, world)
+    score = engine.evaluate(gradient, weights)
+    w_host = engine.to_host(weights) if hasattr(weights, "data_ptr") else np.asarray(weights, dtype=np.float64)
+    params = make_params(gradient, updater, 1.0, regParam, 1.0, 0.0)
+    regVal = engine.initial_regval(params, np.ascontiguousarray(w_host, dtype=np.float64))
+    return Evaluation(score.lossSum, score.count, score.nCorrect if classifier else None, regVal,
+                      score.partLoss, score.partCorrect)
+
 
 # ---------------------------------------------------------------------------------------------
 # The optimizer.
@@ -447,6 +603,12 @@ class ParallelizedSGD:
             self.miniBatchFraction, initialWeights, self.convergenceTol,
             compute_dtype=self.compute_dtype)
         return weights
+
+    def evaluate(self, data: PartitionedData, weights, *, engine=None) -> "Evaluation":
+        """Score `weights` on `data` with this optimizer's gradient, updater and regParam: the loss
+        and objective at those weights, the accuracy of a classifier, per-partition sums
+        (evaluate() below; build extension, the reference's users go through MLlib's models)."""
+        return evaluate(data, self.gradient, self.updater, self.regParam, weights, engine=engine)
 
     # object ParallelizedSGD ---------------------------------------------------------------------
     @staticmethod
