@@ -213,6 +213,46 @@ int32_t psgd_evaluate_device(psgd_ctx* ctx, int32_t gradient, const double* d_w,
 int32_t psgd_predict(psgd_ctx* ctx, int64_t part, const double* w, double* margins);
 int32_t psgd_predict_device(psgd_ctx* ctx, int64_t part, const double* d_w, double* d_margins, void* stream);
 
+/* Column statistics over every registered row (MLlib 1.6.1 Statistics.colStats /
+ * MultivariateOnlineSummarizer) -- what StandardScaler fits on before GeneralizedLinearAlgorithm
+ * optimizes. out holds 1 + 5 d doubles {count, mean[d], m2[d], numNonzeros[d], max[d], min[d]}.
+ * n is the total row count; a CSR row's absent entries count as zeros; values are the stored
+ * values widened to double. For each feature j:
+ *   count          n;
+ *   numNonzeros_j  rows whose stored value is != 0.0 (an explicitly stored 0.0 in CSR does not count);
+ *   mean_j         sum(x) / n;
+ *   m2_j           sum((x - mean_j)^2) over all n rows, implicit zeros included; the summarizer's
+ *                  unbiased variance is m2_j / (n - 1) for n > 1 and 0.0 for n = 1;
+ *   max_j, min_j   over all n rows (a CSR column with numNonzeros_j < n takes part with 0.0).
+ * A column whose n values are all equal has mean_j exactly that value and m2_j exactly 0.0 (so
+ * that a scaler gives it factor 0): on dense rows for any constant; on CSR rows for a column
+ * without non-zeros and for a column holding 1.0 in every row (an appended bias). NaN and Inf
+ * inputs are outside the contract. A registry of empty partitions gives count 0 and zeros.
+ * Reproducibility: dense rows are summed without atomics in an order the registry's geometry
+ * fixes -- every output has the same bits from call to call. CSR rows are summed with fp64 vector
+ * atomics (columns scatter): count, numNonzeros, max and min are exact and reproducible, mean and
+ * m2 may differ in their last bits from run to run.
+ * The calls only read the rows, so they work on every kind of registration, zero-copy included.
+ * Like the scoring calls they wait for registration copies in flight, order themselves against an
+ * epoch running on another stream, use scratch of their own and leave the epoch state alone. The
+ * host-pointer form runs on the context's stream and returns when `out` is written; the _device
+ * form takes a device pointer and a stream (NULL: the context's) and is enqueued without a host
+ * synchronisation (the CSR form accumulates in d_out itself). */
+int32_t psgd_column_stats(psgd_ctx* ctx, double* out);
+int32_t psgd_column_stats_device(psgd_ctx* ctx, double* d_out, void* stream);
+
+/* StandardScalerModel.transform in place on the context's own copy of the rows:
+ *   x'_ij = round_to_storage(((double)x_ij - shift_j) * factor_j),
+ * the subtraction first, and left out entirely when shift is NULL; factor is d long. Dense pad
+ * columns are not touched. CSR: val[k] = round_to_storage((double)val[k] * factor[col[k]]); a
+ * shift would fill the absent entries and is refused (PSGD_EINVAL). PSGD_ESTATE when no partition
+ * is registered, or when any registered partition is a zero-copy one (psgd_register_*_device): the
+ * caller owns those rows and scales them itself. The call keeps no record of what it did: calling
+ * it twice scales twice. Nothing derived from row values is cached on the context across epochs,
+ * so the next epoch or scoring call simply reads the new values. Ordering as for the scoring calls. */
+int32_t psgd_transform_columns(psgd_ctx* ctx, const double* shift, const double* factor);
+int32_t psgd_transform_columns_device(psgd_ctx* ctx, const double* d_shift, const double* d_factor, void* stream);
+
 /* Diagnostics: which chain kernel the last epoch launched (DESIGN.md §3 has the table):
  * 100 + NV   per-sample dense chain (chain_dense), NV 16-byte row vectors per lane;
  * 200 / 201  general dense / CSR chain (chain_general);

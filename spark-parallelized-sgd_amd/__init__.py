@@ -13,14 +13,16 @@ from ._native import (DeviceError, IllegalArgumentException, UnsupportedOperatio
 from .data import (CsrPartition, DensePartition, DeviceCsrPartition, DevicePartition, PartitionedData,
                    shard_range)
 from .gradient import Gradient, HingeGradient, LeastSquaresGradient, LogisticGradient
-from .optimization import (DriverCheckpoint, Evaluation, HipEngine, ParallelizedSGD, ShardedEngine, evaluate,
-                           make_params, runParallelizedSGD)
+from .feature import StandardScaler, StandardScalerModel, column_stats
+from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine, ParallelizedSGD, ShardedEngine,
+                           evaluate, make_params, runParallelizedSGD)
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .util import loadLibSVMFile
 
 __all__ = [
-    "ParallelizedSGD", "runParallelizedSGD", "evaluate", "Evaluation", "HipEngine", "ShardedEngine", "make_params",
+    "ParallelizedSGD", "runParallelizedSGD", "evaluate", "Evaluation", "HipEngine",
+    "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",
     "SGDUpdater", "SimpleSGDUpdater", "SquaredL2SGDUpdater", "L1SGDUpdater",
     "AdaGradSGDUpdater", "AdamSGDUpdater",

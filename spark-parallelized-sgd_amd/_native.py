@@ -29,6 +29,7 @@ EXPORTED = (
     "psgd_vmm_stats", "psgd_reroll_stats", "psgd_libsvm_read", "psgd_libsvm_free",
     "psgd_sample_partition", "psgd_host_alloc", "psgd_host_free", "psgd_register_wait",
     "psgd_evaluate", "psgd_evaluate_device", "psgd_predict", "psgd_predict_device",
+    "psgd_column_stats", "psgd_column_stats_device", "psgd_transform_columns", "psgd_transform_columns_device",
 )
 
 
@@ -122,6 +123,10 @@ def lib():
             "psgd_evaluate_device": ([vp, C.c_int32, vp, vp, vp, vp], C.c_int32),
             "psgd_predict": ([vp, C.c_int64, vp, vp], C.c_int32),
             "psgd_predict_device": ([vp, C.c_int64, vp, vp, vp], C.c_int32),
+            "psgd_column_stats": ([vp, vp], C.c_int32),
+            "psgd_column_stats_device": ([vp, vp, vp], C.c_int32),
+            "psgd_transform_columns": ([vp, vp, vp], C.c_int32),
+            "psgd_transform_columns_device": ([vp, vp, vp, vp], C.c_int32),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -352,3 +357,28 @@ class Context:
 
     def predict_device(self, part: int, w_ptr, margins_ptr, stream=None):
         check(self._L.psgd_predict_device(self.handle, C.c_int64(part), w_ptr, margins_ptr, stream))
+
+    # column statistics and the column transform -------------------------------------------------
+    def column_stats(self, d: int):
+        """Host-pointer form (psgd_column_stats): the 1 + 5 d doubles
+        {count, mean[d], m2[d], numNonzeros[d], max[d], min[d]} over every registered row."""
+        import numpy as np
+        out = np.zeros(1 + 5 * int(d), dtype=np.float64)
+        check(self._L.psgd_column_stats(self.handle, out.ctypes.data))
+        return out
+
+    def column_stats_device(self, out_ptr, stream=None):
+        """psgd_column_stats_device: enqueued on `stream`; out[1 + 5 d] on the device."""
+        check(self._L.psgd_column_stats_device(self.handle, out_ptr, stream))
+
+    def transform_columns(self, shift, factor):
+        """Host-pointer form (psgd_transform_columns): x = ((double)x - shift) * factor in place on
+        the context's own rows; shift may be None. Calling it twice scales twice."""
+        import numpy as np
+        factor = np.ascontiguousarray(factor, dtype=np.float64)
+        shift = None if shift is None else np.ascontiguousarray(shift, dtype=np.float64)
+        check(self._L.psgd_transform_columns(self.handle, None if shift is None else shift.ctypes.data,
+                                             factor.ctypes.data))
+
+    def transform_columns_device(self, shift_ptr, factor_ptr, stream=None):
+        check(self._L.psgd_transform_columns_device(self.handle, shift_ptr, factor_ptr, stream))

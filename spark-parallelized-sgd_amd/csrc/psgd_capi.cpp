@@ -446,6 +446,12 @@ struct psgd_ctx {
     // the host-pointer forms' staging of w, out3 + part_out and a partition's margins
     DevBuf eparts, etiles, epart, ew, emargins;
     std::vector<psgd::EvalPart> eval_parts;
+    // column statistics and the column transform (psgd_column_stats / psgd_transform_columns): the
+    // tiling as uploaded with the descriptors ([P + 1] first tiles), the dense pass's tile records and
+    // their merged spans, and the host-pointer forms' staging of out / shift / factor
+    DevBuf stile0, srec, sio;
+    std::vector<int64_t> stat_tile0;
+    psgd::StatGeom stat_geom{};
 };
 
 namespace {
@@ -627,6 +633,11 @@ int32_t upload_descs(psgd_ctx* ctx, hipStream_t st) {
     const size_t P = ctx->parts.size();
     HIP_TRY(ctx->descs.ensure(std::max<size_t>(P, 1) * sizeof(psgd::ChainDesc)));
     HIP_TRY(ctx->eparts.ensure((P + 1) * sizeof(psgd::EvalPart)));
+    HIP_TRY(ctx->stile0.ensure((P + 1) * sizeof(int64_t)));
+    std::vector<int64_t> st0;
+    st0.reserve(P + 1);
+    psgd::StatGeom gm{};
+    int64_t stiles = 0;
     std::vector<psgd::ChainDesc> h;
     std::vector<psgd::EvalPart> ep;
     h.reserve(P);
@@ -648,12 +659,19 @@ int32_t upload_descs(psgd_ctx* ctx, hipStream_t st) {
         psgd::eval_geometry(q.layout, q.ld * (int64_t)dtype_size(q.dtype), q.max_nnz, &e.tile_rows, &e.group);
         tiles += (q.n_rows + e.tile_rows - 1) / e.tile_rows;
         ep.push_back(e);
+        if (st0.empty()) gm = psgd::stats_geometry(q.layout, q.d, q.dtype == PSGD_F32 ? 1 : 0);
+        st0.push_back(stiles);
+        stiles += (q.n_rows + gm.tile_rows - 1) / gm.tile_rows;
     }
     ep.push_back(psgd::EvalPart{tiles, 1, 64});
+    st0.push_back(stiles);
+    HIP_TRY(hipMemcpyAsync(ctx->stile0.p, st0.data(), st0.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     if (P) HIP_TRY(hipMemcpyAsync(ctx->descs.p, h.data(), P * sizeof(psgd::ChainDesc), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->eparts.p, ep.data(), ep.size() * sizeof(psgd::EvalPart), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     ctx->eval_parts = ep;
+    ctx->stat_tile0 = st0;
+    ctx->stat_geom = gm;
     ctx->descs_dirty = false;
     return PSGD_OK;
 }
@@ -793,6 +811,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->cnt_d, &ctx->cnt, &ctx->steps, &ctx->partial, &ctx->tmp, &ctx->zbuf, &ctx->wf32, &ctx->stamps, &ctx->walpha, &ctx->wnsq0,
                           &ctx->sdescs, &ctx->srows, &ctx->sys, &ctx->xstate,
                           &ctx->eparts, &ctx->etiles, &ctx->epart, &ctx->ew, &ctx->emargins,
+                          &ctx->stile0, &ctx->srec, &ctx->sio,
                           &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
@@ -1671,6 +1690,132 @@ int32_t psgd_predict(psgd_ctx* ctx, int64_t part, const double* w, double* margi
     if (rc) return rc;
     DeviceGuard g(ctx->device);
     HIP_TRY(hipMemcpyAsync(margins, d_m, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+// ---- Column statistics and the column transform (kernels in psgd_colstats.hip) ----
+// The same place in the context as the scoring calls: score_prepare, scratch of their own, no
+// epoch state touched.
+
+int32_t psgd_column_stats_device(psgd_ctx* ctx, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_out) return fail(PSGD_EINVAL, "d_out is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int32_t rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const Part& first = ctx->parts.begin()->second;
+    const psgd::StatGeom& gm = ctx->stat_geom;
+    const int P = (int)ctx->parts.size();
+    const int64_t n_tiles = ctx->stat_tile0.back();
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    int e;
+    if (first.layout == psgd::kCsr) {
+        int64_t n_rows = 0;
+        for (auto& kv : ctx->parts) n_rows += kv.second.n_rows;
+        e = psgd::launch_stats_csr(ctx->descs.as<psgd::ChainDesc>(), ctx->stile0.as<int64_t>(), P, n_tiles, n_rows,
+                                   gm, storage, d_out, ctx->num_cus, st);
+    } else {
+        const int64_t span = psgd::stats_merge_span(n_tiles);
+        const int64_t n_spans = (n_tiles + span - 1) / span;
+        const size_t rec_d = 5 * (size_t)gm.d;
+        HIP_TRY(ctx->srec.ensure(((size_t)(n_tiles + n_spans) * (rec_d + 1) + 1) * sizeof(double)));
+        double* rec = ctx->srec.as<double>();
+        double* rec2 = rec + (size_t)n_tiles * rec_d;
+        double* rec_m = rec2 + (size_t)n_spans * rec_d;
+        double* rec2_m = rec_m + n_tiles;
+        e = psgd::launch_stats_dense(ctx->descs.as<psgd::ChainDesc>(), ctx->stile0.as<int64_t>(), P, n_tiles, gm,
+                                     storage, rec, rec_m, rec2, rec2_m, d_out, ctx->num_cus, st);
+    }
+    if (e) return fail(PSGD_EDEVICE, std::string("column statistics launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_column_stats(psgd_ctx* ctx, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    size_t len = 0;
+    double* d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        len = 1 + 5 * (size_t)ctx->parts.begin()->second.d;
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        int32_t rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->sio.ensure(len * sizeof(double)));
+        d_out = ctx->sio.as<double>();
+    }
+    int32_t rc = psgd_column_stats_device(ctx, d_out, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(out, d_out, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+// What both transform forms refuse (ctx->mu held).
+static int32_t transform_check(psgd_ctx* ctx, bool shift) {
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    for (auto& kv : ctx->parts)
+        if (!kv.second.owned)
+            return fail(PSGD_ESTATE, "partition " + std::to_string(kv.first) +
+                                         " is registered zero-copy: its rows belong to the caller, who scales them");
+    if (shift && ctx->parts.begin()->second.layout == psgd::kCsr)
+        return fail(PSGD_EINVAL, "a shift (withMean) cannot be applied to CSR rows: it would fill the absent entries");
+    return PSGD_OK;
+}
+
+int32_t psgd_transform_columns_device(psgd_ctx* ctx, const double* d_shift, const double* d_factor, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_factor) return fail(PSGD_EINVAL, "d_factor is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int32_t rc = transform_check(ctx, d_shift != nullptr);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const Part& first = ctx->parts.begin()->second;
+    const int e = psgd::launch_transform(ctx->descs.as<psgd::ChainDesc>(), ctx->stile0.as<int64_t>(),
+                                         (int)ctx->parts.size(), ctx->stat_tile0.back(), first.layout, ctx->stat_geom,
+                                         first.dtype == PSGD_F32 ? 1 : 0, d_shift, d_factor, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("column transform launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_transform_columns(psgd_ctx* ctx, const double* shift, const double* factor) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!factor) return fail(PSGD_EINVAL, "factor is null");
+    double *d_shift = nullptr, *d_factor = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        int32_t rc = transform_check(ctx, shift != nullptr);
+        if (rc) return rc;
+        const size_t d = (size_t)ctx->parts.begin()->second.d;
+        DeviceGuard g(ctx->device);
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        // (beside the statistics' staging of out, so that a fit-then-transform does not reallocate)
+        HIP_TRY(ctx->sio.ensure((1 + 5 * d) * sizeof(double)));
+        d_factor = ctx->sio.as<double>();
+        HIP_TRY(hipMemcpyAsync(d_factor, factor, d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        if (shift) {
+            d_shift = d_factor + d;
+            HIP_TRY(hipMemcpyAsync(d_shift, shift, d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        }
+        // the caller's arrays are pageable in general: the copies have left them when this returns
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    int32_t rc = psgd_transform_columns_device(ctx, d_shift, d_factor, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PSGD_OK;
 }

@@ -191,4 +191,33 @@ int launch_score(const ChainDesc* descs, const EvalPart* ep, int n_parts, int64_
 int launch_eval_reduce(const ChainDesc* descs, const EvalPart* ep, int n_parts, const double* tile_loss,
                        const double* tile_ok, double* part, double* part_out, double* out3, hipStream_t st);
 
+// ---- Column statistics and the column transform (psgd_colstats.hip) ----
+// The tiling of these passes: the same for every partition of a registry (one d, one storage).
+// tile0[p] (device, [n_parts + 1]) is partition p's first tile, the tiles numbered across the
+// partitions in partition-index order; entry n_parts is the number of tiles.
+struct StatGeom {
+    int32_t d;
+    int32_t nvec;       // dense: 16-byte vectors that hold a row's d features
+    int32_t group;      // dense: lanes across a row (a power of two; 64 / group rows a wave instruction)
+    int32_t n_chunks;   // dense statistics: column chunks (2 KiB of a row) a tile is cut into
+    int32_t tile_rows;
+};
+StatGeom stats_geometry(int layout, int d, int storage);
+// The records of stats_dense are merged in two levels: spans of this many consecutive tiles first.
+int64_t stats_merge_span(int64_t n_tiles);
+// out[1 + 5 d] = {count, mean[d], m2[d], numNonzeros[d], max[d], min[d]} over every row. Dense:
+// rec [n_tiles * 5 d] + rec_m [n_tiles] and rec2 [n_spans * 5 d] + rec2_m [n_spans] are scratch
+// (n_spans = ceil(n_tiles / stats_merge_span(n_tiles))); no atomics, reproducible bits. CSR: `out`
+// itself is the accumulator of fp64 atomics (mean and m2 not reproducible to the last bit).
+int launch_stats_dense(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
+                       const StatGeom& gm, int storage, double* rec, double* rec_m, double* rec2, double* rec2_m,
+                       double* out, int num_cus, hipStream_t st);
+int launch_stats_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles, int64_t n_rows,
+                     const StatGeom& gm, int storage, double* out, int num_cus, hipStream_t st);
+// In place on the partitions' rows: x = round_to_storage(((double)x - shift[c]) * factor[c]);
+// shift is nullable (and must be null for CSR); dense pad columns [d, ld) are left alone.
+int launch_transform(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles, int layout,
+                     const StatGeom& gm, int storage, const double* shift, const double* factor, int num_cus,
+                     hipStream_t st);
+
 }  // namespace psgd

@@ -103,6 +103,9 @@ class PartitionedData:
             raise IllegalArgumentException(
                 f"requirement failed: all rows must have the same size, got {sorted(feats)}")
         self._num_features = feats.pop() if feats else 0
+        # (shift | None, factor): a StandardScalerModel.transform the engine applies to its device
+        # copy of the rows right after registering them (feature.py); None: the rows as they are
+        self.column_transform = None
 
     # RDD-like API ----------------------------------------------------------------------------
     def count(self) -> int:

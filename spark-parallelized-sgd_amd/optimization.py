@@ -205,7 +205,25 @@ class HipEngine(ShardedEngine):
                                              part.val.data_ptr(), dt)
             else:
                 raise IllegalArgumentException(f"unsupported partition type {type(part).__name__}")
+        self._apply_column_transform(data)
         self.ctx.registered_token = key
+
+    def _apply_column_transform(self, data: PartitionedData):
+        """The data set's StandardScalerModel.transform, if it carries one: scales the context's
+        fresh copy of the rows in place (psgd_transform_columns_device on self.stream), once per
+        registration -- the token is set only afterwards, so no epoch or scoring call of any engine
+        sees unscaled rows (ctx.engine_lock held)."""
+        tr = getattr(data, "column_transform", None)
+        if tr is None or self.n_local == 0:
+            return
+        shift, factor = tr
+        torch = self.torch
+        with torch.cuda.stream(self.stream):
+            f = torch.from_numpy(np.ascontiguousarray(factor, dtype=np.float64)).to(self.dev)
+            s = None if shift is None else torch.from_numpy(np.ascontiguousarray(shift, dtype=np.float64)).to(self.dev)
+            self.ctx.transform_columns_device(None if s is None else s.data_ptr(), f.data_ptr(),
+                                              self.stream.cuda_stream)
+        self.stream.synchronize()   # f and s are temporaries of this call
 
     # driver hooks ---------------------------------------------------------------------------
     def weights(self, w_host: np.ndarray):
@@ -469,7 +487,70 @@ class HipEngine(ShardedEngine):
         return out
 
 
+    # column statistics (psgd_column_stats_device) ----------------------------------------------
+    def column_stats(self) -> "ColumnStats":
+        """Statistics.colStats over every partition of the data, on all ranks (one streaming fp64
+        pass over dense rows, two over CSR rows; include/psgd.h has the semantics). Each rank runs
+        its partitions; the ranks all-gather their 1 + 5 d doubles (the backends of exchange()) and
+        every rank merges them on the host in rank order with Chan's formula in fp64: counts and
+        numNonzeros add, max and min are taken, a rank with count 0 is skipped. count 0 raises the
+        summarizer's IllegalArgumentException."""
+        torch = self.torch
+        nf = self._data.num_features
+        width = 1 + 5 * nf
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            buf = torch.zeros(width, dtype=torch.float64, device=self.dev)
+            if self.n_local > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    self.ctx.column_stats_device(buf.data_ptr(), self.stream.cuda_stream)
+            if self.world > 1:
+                import torch.distributed as dist
+                out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
+                if dist.get_backend() == "gloo":
+                    dist.all_gather(list(out.view(self.world, width).unbind(0)), buf)
+                else:
+                    dist.all_gather_into_tensor(out, buf)
+                h = out.cpu().numpy().reshape(self.world, width)
+            else:
+                h = buf.cpu().numpy().reshape(1, width)
+        return merge_column_stats(h, nf)
+
+
+def merge_column_stats(h: np.ndarray, d: int) -> "ColumnStats":
+    """Rows of {count, mean[d], m2[d], numNonzeros[d], max[d], min[d]} merged in row order with
+    Chan's formula in fp64 (MultivariateOnlineSummarizer.merge); rows with count 0 are skipped."""
+    n = 0.0
+    mean = m2 = nnz = mx = mn = None
+    for row in np.asarray(h, dtype=np.float64).reshape(-1, 1 + 5 * d):
+        nb = float(row[0])
+        if nb == 0.0:
+            continue
+        b = row[1:].reshape(5, d)
+        if n == 0.0:
+            n, mean, m2, nnz, mx, mn = nb, b[0].copy(), b[1].copy(), b[2].copy(), b[3].copy(), b[4].copy()
+            continue
+        tot = n + nb
+        delta = b[0] - mean
+        mean = mean + delta * (nb / tot)
+        m2 = m2 + b[1] + delta * delta * (n * nb / tot)
+        nnz = nnz + b[2]
+        mx = np.maximum(mx, b[3])
+        mn = np.minimum(mn, b[4])
+        n = tot
+    if n == 0.0:
+        raise IllegalArgumentException("requirement failed: Nothing has been added to this summarizer.")
+    variance = m2 / (n - 1.0) if n > 1.0 else np.zeros(d)
+    return ColumnStats(int(n), mean, variance, nnz.astype(np.int64), mx, mn)
+
+
 EngineScore = collections.namedtuple("EngineScore", "lossSum count nCorrect partLoss partCorrect")
+# Statistics.colStats (MultivariateStatisticalSummary): count, and per feature mean, the unbiased
+# variance, numNonzeros, max and min.
+ColumnStats = collections.namedtuple("ColumnStats", "count mean variance numNonzeros max min")
 
 
 class Evaluation:
@@ -757,7 +838,7 @@ _CKPT_VERSION = 1
 
 def _ckpt_fingerprint(params, data: PartitionedData, w0: np.ndarray) -> np.ndarray:
     """What an iteration's result depends on besides (w, i): the plugins and hyper-parameters
-    (the psgd_params fields), the data's shape, the initial weights (the first regVal and the
+    (the psgd_params fields), the data's shape and column transform, the initial weights (the first regVal and the
     driver's first convergence reference). numIterations is left out, so a finished run can be
     resumed with a larger iteration budget and continue exactly where it stopped."""
     import hashlib
@@ -767,6 +848,14 @@ def _ckpt_fingerprint(params, data: PartitionedData, w0: np.ndarray) -> np.ndarr
             h.update(f"{f}={getattr(params, f)!r};".encode())
     h.update(f"n={data.count()};P={data.num_partitions};d={data.num_features};".encode())
     h.update(np.ascontiguousarray(w0, dtype=np.float64).tobytes())
+    # a column transform the data carries (StandardScalerModel.transform) changes every row the
+    # chains read: a checkpoint of scaled data must not resume on unscaled data
+    tr = getattr(data, "column_transform", None)
+    if tr is not None:
+        shift, factor = tr
+        h.update(b"transform;shift=" + (b"none" if shift is None else
+                                       np.ascontiguousarray(shift, dtype=np.float64).tobytes()))
+        h.update(b";factor=" + np.ascontiguousarray(factor, dtype=np.float64).tobytes())
     return np.frombuffer(h.digest(), dtype=np.uint8)
 
 
