@@ -253,6 +253,55 @@ int32_t psgd_column_stats_device(psgd_ctx* ctx, double* d_out, void* stream);
 int32_t psgd_transform_columns(psgd_ctx* ctx, const double* shift, const double* factor);
 int32_t psgd_transform_columns_device(psgd_ctx* ctx, const double* d_shift, const double* d_factor, void* stream);
 
+/* The batch gradient at fixed weights w (d long) -- what MLlib 1.6.1 GradientDescent.runMiniBatchSGD
+ * and LBFGS's CostFun aggregate per iteration: over the batch rows of every registered partition,
+ *   out[0 .. d)  gradientSum_j = sum_i mult_i x_ij,
+ *   out[d]       lossSum = sum_i loss_i,
+ *   out[d + 1]   (double)count,
+ * with (loss_i, mult_i) the binary Gradient.compute(x_i, y_i, w) of `gradient`
+ * (PSGD_GRADIENT_LOGISTIC / _LEAST_SQUARES / _HINGE), all in fp64 whatever the storage.
+ * The batch: mini_batch_fraction >= 1 takes every row; <= 0 takes none (zeros, count 0, PSGD_OK);
+ * otherwise it is RDD.sample(false, fraction, 42 + iteration) per partition -- the rows an epoch
+ * of the same fraction and iteration visits. A sampled batch over a partition of more than
+ * 2^31 - 1 rows is PSGD_EUNSUPPORTED, as for the epoch.
+ * Reproducibility: dense rows are summed without atomics in an order the registry's geometry fixes
+ * (a tile of rows by one wave, the tiles in partition-index order): every output has the same bits
+ * from call to call. Registering the same rows as more or fewer partitions changes the tiling and
+ * so the last bits. CSR rows: lossSum and count are reproducible; gradientSum is added with fp64
+ * vector atomics (columns scatter) and may differ in its last bits from run to run.
+ * Errors: PSGD_EINVAL for a null ctx or pointer, an unknown gradient or a fraction outside [0, 1];
+ * PSGD_ESTATE when no partition is registered. A registry of empty partitions gives zeros.
+ * The calls only read the rows (any kind of registration). Like the scoring calls they wait for
+ * registration copies in flight, order themselves against an epoch running on another stream, use
+ * scratch and sampler buffers of their own and leave the epoch state alone (psgd_ctx_last_kernel,
+ * psgd_ctx_chain_launches and the chain times are unchanged). The host-pointer form runs on the
+ * context's stream and returns when `out` is written. The _device form takes device pointers and a
+ * stream (NULL: the context's) and is enqueued without a host synchronisation when the batch is
+ * every row; a sampled batch waits once for its sampler's seeds to reach the device. */
+int32_t psgd_gradient_sum(psgd_ctx* ctx, int32_t gradient, const double* w, double mini_batch_fraction,
+                          int32_t iteration, double* out);
+int32_t psgd_gradient_sum_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double mini_batch_fraction,
+                                 int32_t iteration, double* d_out, void* stream);
+
+/* One GradientDescent update from a psgd_gradient_sum result `sum` (d + 2 doubles):
+ *   (w_out, *regval_out) = updater.compute(w, sum[0 .. d) / sum[d + 1], step_size, iteration, reg_param)
+ * for the stateless updaters, MLlib's SimpleUpdater / SquaredL2Updater / L1Updater, with
+ * thisIterStepSize = step_size / sqrt(iteration): Simple w - s g, regVal 0; SquaredL2
+ * w (1 - s reg) - s g, regVal 0.5 reg ||w_out||^2; L1 soft-thresholding of w - s g by s reg, regVal
+ * reg ||w_out||_1. The mean gradient is a division by the count, as in MLlib; the norms are summed
+ * in a fixed order (the same bits from call to call). w_out may be w.
+ * Errors: PSGD_EUNSUPPORTED for AdaGrad and Adam (they keep a status; MLlib's GradientDescent takes
+ * none); PSGD_EINVAL for a null ctx or pointer, an unknown updater, d <= 0, iteration < 1 and, in
+ * the host-pointer form, a count <= 0 (the _device form cannot see the count: its caller skips the
+ * update of an empty batch, as runMiniBatchSGD does). No partition need be registered. Ordering and
+ * scratch as for psgd_gradient_sum. */
+int32_t psgd_gd_update(psgd_ctx* ctx, int32_t updater, int32_t d, const double* w, const double* sum,
+                       double step_size, int32_t iteration, double reg_param, double* w_out,
+                       double* regval_out);
+int32_t psgd_gd_update_device(psgd_ctx* ctx, int32_t updater, int32_t d, const double* d_w, const double* d_sum,
+                              double step_size, int32_t iteration, double reg_param, double* d_w_out,
+                              double* d_regval_out, void* stream);
+
 /* Diagnostics: which chain kernel the last epoch launched (DESIGN.md §3 has the table):
  * 100 + NV   per-sample dense chain (chain_dense), NV 16-byte row vectors per lane;
  * 200 / 201  general dense / CSR chain (chain_general);

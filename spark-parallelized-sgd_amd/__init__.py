@@ -16,12 +16,14 @@ from .gradient import Gradient, HingeGradient, LeastSquaresGradient, LogisticGra
 from .feature import StandardScaler, StandardScalerModel, column_stats
 from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine, ParallelizedSGD, ShardedEngine,
                            evaluate, make_params, runParallelizedSGD)
+from .gradient_descent import GradientDescent, GradientSum, gradient_sum, runMiniBatchSGD
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .util import loadLibSVMFile
 
 __all__ = [
     "ParallelizedSGD", "runParallelizedSGD", "evaluate", "Evaluation", "HipEngine",
+    "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",
     "SGDUpdater", "SimpleSGDUpdater", "SquaredL2SGDUpdater", "L1SGDUpdater",

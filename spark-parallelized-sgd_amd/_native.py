@@ -30,6 +30,7 @@ EXPORTED = (
     "psgd_sample_partition", "psgd_host_alloc", "psgd_host_free", "psgd_register_wait",
     "psgd_evaluate", "psgd_evaluate_device", "psgd_predict", "psgd_predict_device",
     "psgd_column_stats", "psgd_column_stats_device", "psgd_transform_columns", "psgd_transform_columns_device",
+    "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
 )
 
 
@@ -127,6 +128,12 @@ def lib():
             "psgd_column_stats_device": ([vp, vp, vp], C.c_int32),
             "psgd_transform_columns": ([vp, vp, vp], C.c_int32),
             "psgd_transform_columns_device": ([vp, vp, vp, vp], C.c_int32),
+            "psgd_gradient_sum": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp], C.c_int32),
+            "psgd_gradient_sum_device": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp, vp], C.c_int32),
+            "psgd_gd_update": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, dp],
+                               C.c_int32),
+            "psgd_gd_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp,
+                                       vp], C.c_int32),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -382,3 +389,35 @@ class Context:
 
     def transform_columns_device(self, shift_ptr, factor_ptr, stream=None):
         check(self._L.psgd_transform_columns_device(self.handle, shift_ptr, factor_ptr, stream))
+
+    # the batch gradient and the batch update ----------------------------------------------------
+    def gradient_sum(self, gradient: int, w, fraction: float = 1.0, iteration: int = 0):
+        """Host-pointer form (psgd_gradient_sum): the d + 2 doubles {gradientSum[d], lossSum, count}
+        of host weights w over the batch (every row, or RDD.sample(false, fraction, 42 + iteration))."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        out = np.zeros(w.shape[0] + 2, dtype=np.float64)
+        check(self._L.psgd_gradient_sum(self.handle, int(gradient), w.ctypes.data, float(fraction), int(iteration),
+                                        out.ctypes.data))
+        return out
+
+    def gradient_sum_device(self, gradient: int, w_ptr, fraction, iteration, out_ptr, stream=None):
+        """psgd_gradient_sum_device: enqueued on `stream`; out[d + 2] on the device."""
+        check(self._L.psgd_gradient_sum_device(self.handle, int(gradient), w_ptr, float(fraction), int(iteration),
+                                               out_ptr, stream))
+
+    def gd_update(self, updater: int, w, gsum, step: float, iteration: int, reg: float):
+        """Host-pointer form (psgd_gd_update): (w', regVal) of one GradientDescent update."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        gsum = np.ascontiguousarray(gsum, dtype=np.float64)
+        out = np.zeros_like(w)
+        rv = C.c_double()
+        check(self._L.psgd_gd_update(self.handle, int(updater), int(w.shape[0]), w.ctypes.data, gsum.ctypes.data,
+                                     float(step), int(iteration), float(reg), out.ctypes.data, C.byref(rv)))
+        return out, rv.value
+
+    def gd_update_device(self, updater: int, d: int, w_ptr, sum_ptr, step, iteration, reg, w_out_ptr, regval_ptr,
+                         stream=None):
+        check(self._L.psgd_gd_update_device(self.handle, int(updater), int(d), w_ptr, sum_ptr, float(step),
+                                            int(iteration), float(reg), w_out_ptr, regval_ptr, stream))

@@ -452,6 +452,11 @@ struct psgd_ctx {
     DevBuf stile0, srec, sio;
     std::vector<int64_t> stat_tile0;
     psgd::StatGeom stat_geom{};
+    // the batch gradient and the batch update (psgd_gradient_sum / psgd_gd_update): a sampled
+    // batch's descriptors, rows, labels and sampler states (never an epoch's sdescs / srows / sys),
+    // the tile records with the two-pass path's multipliers and the update's block sums, and the
+    // host-pointer forms' staging
+    DevBuf gdescs, grows, gys, gxstate, grec, gio;
 };
 
 namespace {
@@ -812,6 +817,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->sdescs, &ctx->srows, &ctx->sys, &ctx->xstate,
                           &ctx->eparts, &ctx->etiles, &ctx->epart, &ctx->ew, &ctx->emargins,
                           &ctx->stile0, &ctx->srec, &ctx->sio,
+                          &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
                           &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
@@ -1154,6 +1160,21 @@ static int32_t mirror_address(psgd_ctx* ctx, double* h, double** dev) {
 static int32_t run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const double* d_w_in,
                                 double* d_partial, int64_t* d_chain_counts, void* stream, double* mirror);
 
+// RDD.sample(false, f, 42 + iteration): one XORShiftRandom per registered partition, seeded as
+// PartitionwiseSampledRDD does -- the p-th java.util.Random(42 + iteration).nextLong() for
+// partition index p, through hashSeed (ctx->mu held).
+static std::vector<uint64_t> sampler_states(psgd_ctx* ctx, int32_t iteration) {
+    std::vector<uint64_t> xs(ctx->parts.size());
+    sampling::JavaRandom jr(42 + (int64_t)iteration);
+    int64_t drawn = 0, s = 0;
+    size_t c = 0;
+    for (auto& kv : ctx->parts) {
+        while (drawn <= kv.first) { s = jr.next_long(); ++drawn; }
+        xs[c++] = (uint64_t)sampling::xorshift_hash_seed(s);
+    }
+    return xs;
+}
+
 int32_t psgd_run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const double* d_w_in,
                               double* d_partial, int64_t* d_chain_counts, void* stream) {
     return run_epoch_device(ctx, params, d_w_in, d_partial, d_chain_counts, stream, nullptr);
@@ -1226,16 +1247,7 @@ static int32_t run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const 
     psgd::ChainLaunch L;
     L.descs = ctx->descs.as<psgd::ChainDesc>();
     if (sampled) {
-        // one XORShiftRandom per partition, seeded as PartitionwiseSampledRDD does: the p-th
-        // java.util.Random(42 + i).nextLong() for partition index p, through hashSeed
-        std::vector<uint64_t> xs((size_t)P);
-        sampling::JavaRandom jr(42 + (int64_t)params->iteration);
-        int64_t drawn = 0, s = 0;
-        size_t c = 0;
-        for (auto& kv : ctx->parts) {
-            while (drawn <= kv.first) { s = jr.next_long(); ++drawn; }
-            xs[c++] = (uint64_t)sampling::xorshift_hash_seed(s);
-        }
+        const std::vector<uint64_t> xs = sampler_states(ctx, params->iteration);
         const int64_t stride = std::max<int64_t>(n_max, 1);
         HIP_TRY(ctx->sdescs.ensure((size_t)P * sizeof(psgd::ChainDesc)));
         HIP_TRY(ctx->srows.ensure((size_t)P * (size_t)stride * sizeof(int32_t)));
@@ -1756,6 +1768,194 @@ int32_t psgd_column_stats(psgd_ctx* ctx, double* out) {
     DeviceGuard g(ctx->device);
     HIP_TRY(hipMemcpyAsync(out, d_out, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+// ---- The batch gradient at fixed weights and the batch update (kernels in psgd_grad.hip) ----
+// The same place in the context as the scoring calls: score_prepare, scratch and sampler buffers of
+// their own, no epoch state touched.
+
+static int32_t gradient_args(int32_t gradient, double fraction) {
+    if (gradient < PSGD_GRADIENT_LOGISTIC || gradient > PSGD_GRADIENT_HINGE)
+        return fail(PSGD_EINVAL, "unknown gradient kind " + std::to_string(gradient));
+    if (!(fraction >= 0.0 && fraction <= 1.0)) {
+        char buf[128];
+        snprintf(buf, sizeof buf, "requirement failed: Sampling fraction (%g) must be on interval [0, 1]", fraction);
+        return fail(PSGD_EINVAL, buf);
+    }
+    return PSGD_OK;
+}
+
+int32_t psgd_gradient_sum_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double mini_batch_fraction,
+                                 int32_t iteration, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = gradient_args(gradient, mini_batch_fraction);
+    if (rc) return rc;
+    if (!d_w || !d_out) return fail(PSGD_EINVAL, "d_w/d_out are null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const Part& first = ctx->parts.begin()->second;
+    const int32_t d = first.d;
+    const int P = (int)ctx->parts.size();
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    if (mini_batch_fraction <= 0.0) {   // RDD.sample(false, 0, .): every partition's batch is empty
+        HIP_TRY(hipMemsetAsync(d_out, 0, ((size_t)d + 2) * sizeof(double), st));
+        return PSGD_OK;
+    }
+    int64_t n_max = 0, max_nnz = 0;
+    for (auto& kv : ctx->parts) {
+        n_max = std::max(n_max, kv.second.n_rows);
+        max_nnz = std::max(max_nnz, kv.second.max_nnz);
+    }
+    const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>();
+    if (mini_batch_fraction < 1.0) {
+        // the sampled batch's row indices are int32 (ChainDesc::rows)
+        if (n_max > (int64_t)INT32_MAX)
+            return fail(PSGD_EUNSUPPORTED, "miniBatchFraction < 1 on a partition of more than 2^31 - 1 rows");
+        const std::vector<uint64_t> xs = sampler_states(ctx, iteration);
+        const int64_t stride = std::max<int64_t>(n_max, 1);
+        HIP_TRY(ctx->gdescs.ensure((size_t)P * sizeof(psgd::ChainDesc)));
+        HIP_TRY(ctx->grows.ensure((size_t)P * (size_t)stride * sizeof(int32_t)));
+        HIP_TRY(ctx->gys.ensure((size_t)P * (size_t)stride * sizeof(double)));
+        HIP_TRY(ctx->gxstate.ensure((size_t)P * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpyAsync(ctx->gxstate.p, xs.data(), (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        const int e = psgd::launch_sample(descs, ctx->gdescs.as<psgd::ChainDesc>(), ctx->gxstate.as<uint64_t>(),
+                                          mini_batch_fraction, ctx->grows.as<int32_t>(), ctx->gys.as<double>(), stride,
+                                          P, st);
+        if (e) return fail(PSGD_EDEVICE, "sample kernel launch failed");
+        // the sampler states leave a host vector of this call: wait for the copy
+        HIP_TRY(hipStreamSynchronize(st));
+        descs = ctx->gdescs.as<psgd::ChainDesc>();
+    }
+    // the statistics passes' tiling (a sampled batch keeps it: its tiles past the batch's end are empty)
+    const int64_t n_tiles = ctx->stat_tile0.back();
+    const psgd::GradGeom gm = psgd::grad_geometry(first.layout, d, storage, max_nnz, ctx->stat_geom.tile_rows);
+    const int64_t span = psgd::grad_merge_span(std::max<int64_t>(n_tiles, 1));
+    const int64_t n_spans = (std::max<int64_t>(n_tiles, 1) + span - 1) / span;
+    int e;
+    if (first.layout == psgd::kCsr) {
+        HIP_TRY(ctx->grec.ensure((size_t)(n_tiles + n_spans + 1) * 2 * sizeof(double)));
+        double* rec = ctx->grec.as<double>();
+        e = psgd::launch_gradient_csr(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage, gradient,
+                                      psgd::grad_csr_lds_applies(d), d_w, rec, rec + 2 * (size_t)n_tiles, d_out,
+                                      ctx->num_cus, st);
+    } else {
+        const size_t W = (size_t)d + 2;
+        const size_t mult = gm.fused ? 0 : (size_t)n_tiles * (size_t)gm.tile_rows;
+        HIP_TRY(ctx->grec.ensure(((size_t)(n_tiles + n_spans) * W + mult + 1) * sizeof(double)));
+        double* rec = ctx->grec.as<double>();
+        double* rec2 = rec + (size_t)n_tiles * W;
+        e = psgd::launch_gradient_dense(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage, gradient, d_w, rec,
+                                        rec2, rec2 + (size_t)n_spans * W, d_out, ctx->num_cus, st);
+    }
+    if (e) return fail(PSGD_EDEVICE, std::string("gradient launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_gradient_sum(psgd_ctx* ctx, int32_t gradient, const double* w, double mini_batch_fraction,
+                          int32_t iteration, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = gradient_args(gradient, mini_batch_fraction);
+    if (rc) return rc;
+    if (!w || !out) return fail(PSGD_EINVAL, "w/out are null");
+    size_t d = 0;
+    double *d_w = nullptr, *d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        d = (size_t)ctx->parts.begin()->second.d;
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->gio.ensure((3 * d + 4) * sizeof(double)));
+        d_w = ctx->gio.as<double>();
+        d_out = d_w + d;
+        HIP_TRY(hipMemcpyAsync(d_w, w, d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        // the caller's array is pageable in general: the copy has left it when this returns
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    rc = psgd_gradient_sum_device(ctx, gradient, d_w, mini_batch_fraction, iteration, d_out, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(out, d_out, (d + 2) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+static int32_t gd_update_args(int32_t updater, int32_t d, int32_t iteration) {
+    if (updater < PSGD_UPDATER_SIMPLE || updater > PSGD_UPDATER_ADAM)
+        return fail(PSGD_EINVAL, "unknown updater kind " + std::to_string(updater));
+    if (updater == PSGD_UPDATER_ADAGRAD || updater == PSGD_UPDATER_ADAM)
+        return fail(PSGD_EUNSUPPORTED, "the batch update takes a stateless updater (Simple, SquaredL2, L1): "
+                                       "AdaGrad and Adam keep a status per chain");
+    if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
+    if (iteration < 1) return fail(PSGD_EINVAL, "iteration must be >= 1");
+    return PSGD_OK;
+}
+
+int32_t psgd_gd_update_device(psgd_ctx* ctx, int32_t updater, int32_t d, const double* d_w, const double* d_sum,
+                              double step_size, int32_t iteration, double reg_param, double* d_w_out,
+                              double* d_regval_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = gd_update_args(updater, d, iteration);
+    if (rc) return rc;
+    if (!d_w || !d_sum || !d_w_out || !d_regval_out) return fail(PSGD_EINVAL, "a pointer is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = scratch_acquire(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    // (the block sums live at the end of the staging buffer, beyond the host forms' w / sum / out)
+    const size_t nb = (size_t)psgd::gd_update_blocks(d);
+    const size_t io = 3 * (size_t)d + 4;
+    HIP_TRY(ctx->gio.ensure((io + nb) * sizeof(double)));
+    const double s = step_size / std::sqrt((double)iteration);   // thisIterStepSize (UPD.scala:91)
+    const int e = psgd::launch_gd_update(updater, d, d_w, d_sum, s, reg_param, d_w_out, ctx->gio.as<double>() + io,
+                                         d_regval_out, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("update launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_gd_update(psgd_ctx* ctx, int32_t updater, int32_t d, const double* w, const double* sum,
+                       double step_size, int32_t iteration, double reg_param, double* w_out, double* regval_out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = gd_update_args(updater, d, iteration);
+    if (rc) return rc;
+    if (!w || !sum || !w_out || !regval_out) return fail(PSGD_EINVAL, "a pointer is null");
+    if (!(sum[d + 1] > 0.0)) return fail(PSGD_EINVAL, "the batch is empty (count <= 0): there is no mean gradient");
+    double* base = nullptr;
+    const size_t n = (size_t)d;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DeviceGuard g(ctx->device);
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        // (sized for the block sums too, so that the device form below does not reallocate)
+        HIP_TRY(ctx->gio.ensure((3 * n + 4 + (size_t)psgd::gd_update_blocks(d)) * sizeof(double)));
+        base = ctx->gio.as<double>();
+        HIP_TRY(hipMemcpyAsync(base, w, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(base + n, sum, (n + 2) * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    // {w[d], sum[d + 2], regval, pad, w_out[d]}: the new weights next to the regVal, one copy back
+    double* d_reg = base + 2 * n + 2;
+    double* d_wo = base + 2 * n + 4;
+    rc = psgd_gd_update_device(ctx, updater, d, base, base + n, step_size, iteration, reg_param, d_wo, d_reg,
+                               ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    std::vector<double> h(n + 2);
+    HIP_TRY(hipMemcpyAsync(h.data(), d_reg, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *regval_out = h[0];
+    std::memcpy(w_out, h.data() + 2, n * sizeof(double));
     return PSGD_OK;
 }
 

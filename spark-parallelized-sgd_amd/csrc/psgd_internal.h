@@ -220,4 +220,37 @@ int launch_transform(const ChainDesc* descs, const int64_t* tile0, int n_parts, 
                      const StatGeom& gm, int storage, const double* shift, const double* factor, int num_cus,
                      hipStream_t st);
 
+// ---- The batch gradient at fixed weights and the batch update (psgd_grad.hip) ----
+// The passes run over the statistics passes' tiles (tile0 / tile_rows above). A sampled batch
+// (descriptors with `rows`) keeps the whole partitions' tiling: its tiles past the batch's end are empty.
+struct GradGeom {
+    int32_t d;
+    int32_t nvec;       // dense: 16-byte vectors that hold a row's d features
+    int32_t group;      // lanes across a row (a power of two); CSR: 16, 32 or 64 by the longest row
+    int32_t nvl;        // dense: vectors of a row a lane owns in the fused kernel (1, 2, 4, 8, ..)
+    int32_t fused;      // dense: nvl <= 8 (d <= 2,048 f32, d <= 1,024 f64); else the two-pass path
+    int32_t n_chunks;   // dense two-pass: column chunks (128 vectors) a tile is cut into
+    int32_t tile_rows;
+};
+GradGeom grad_geometry(int layout, int d, int storage, int64_t max_nnz, int tile_rows);
+// The tiles' records are merged in two levels: spans of this many consecutive tiles first.
+int64_t grad_merge_span(int64_t n_tiles);
+// CSR: the LDS-accumulator path applies (d fits a workgroup's LDS and PSGD_GRAD_CSR_GLOBAL is unset).
+bool grad_csr_lds_applies(int d);
+// out[d + 2] = {gradientSum[d], lossSum, count} over the batch rows of descs[0 .. n_parts) at
+// weights w[d]. Dense: rec [n_tiles * (d + 2)] and rec2 [n_spans * (d + 2)] are scratch, and mult
+// [n_tiles * tile_rows] when !gm.fused; no atomics, reproducible bits. CSR: rec [n_tiles * 2], rec2
+// [n_spans * 2]; out[0 .. d) is the accumulator of fp64 atomics. -2: unknown gradient.
+int launch_gradient_dense(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
+                          const GradGeom& gm, int storage, int gradient, const double* w, double* rec, double* rec2,
+                          double* mult, double* out, int num_cus, hipStream_t st);
+int launch_gradient_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
+                        const GradGeom& gm, int storage, int gradient, bool lds, const double* w, double* rec,
+                        double* rec2, double* out, int num_cus, hipStream_t st);
+// w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
+// the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
+int64_t gd_update_blocks(int d);
+int launch_gd_update(int updater, int d, const double* w, const double* sum, double s, double reg, double* w_out,
+                     double* part, double* regval, hipStream_t st);
+
 }  // namespace psgd

@@ -519,6 +519,75 @@ class HipEngine(ShardedEngine):
                 h = buf.cpu().numpy().reshape(1, width)
         return merge_column_stats(h, nf)
 
+    # the batch gradient and the batch update (psgd_gradient_sum_device / psgd_gd_update_device) ---
+    def gradient_sum(self, gradient, w, miniBatchFraction: float = 1.0, iteration: int = 0):
+        """{gradientSum[d], lossSum, count} of weights w over the batch -- every row, or
+        RDD.sample(false, miniBatchFraction, 42 + iteration) per partition -- on all ranks, as a device
+        tensor of d + 2 doubles (include/psgd.h has the semantics). Each rank runs its partitions; the
+        ranks all-gather their d + 2 doubles (the backends of exchange()) and every rank adds the rows
+        in rank order (merge_gradient_sums: a loop, not a tree), so all ranks hold the same bits; a
+        rank without partitions contributes zeros. w: a host array or a device tensor."""
+        if num_classes(gradient) > 2:
+            raise N.UnsupportedOperationException(
+                "gradient_sum with the multinomial LogisticGradient (numClasses > 2) is not built")
+        kind = gradient_kind(gradient)
+        torch = self.torch
+        width = self._data.num_features + 2
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            w_dev = self._score_weights(w)
+            buf = torch.zeros(width, dtype=torch.float64, device=self.dev)
+            if self.n_local > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    self.ctx.gradient_sum_device(kind, w_dev.data_ptr(), miniBatchFraction, iteration,
+                                                 buf.data_ptr(), self.stream.cuda_stream)
+            if self.world > 1:
+                import torch.distributed as dist
+                out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
+                if dist.get_backend() == "gloo":
+                    dist.all_gather(list(out.view(self.world, width).unbind(0)), buf)
+                else:
+                    dist.all_gather_into_tensor(out, buf)
+                buf = merge_gradient_sums(out.view(self.world, width))
+            keep = torch.cuda.Event()
+            keep.record(self.stream)
+        caller.wait_stream(self.stream)
+        buf.record_stream(caller)
+        keep.synchronize()   # w_dev may be a temporary of this call
+        return buf
+
+    def batch_scalars(self, gsum) -> Tuple[float, int]:
+        """(lossSum, count) of a gradient_sum result."""
+        with self.torch.cuda.stream(self.stream):
+            h = gsum[-2:].cpu().numpy()
+        return float(h[0]), int(h[1])
+
+    def gd_update(self, updater, w_dev, gsum, stepSize: float, iteration: int, regParam: float):
+        """(w', regVal) = updater.compute(w, gradientSum / count, stepSize, iteration, regParam) on the
+        device (psgd_gd_update_device); w' is a new device tensor."""
+        torch = self.torch
+        # order after whatever produced the inputs on the caller's stream
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            out = torch.empty(w_dev.shape[0] + 1, dtype=torch.float64, device=self.dev)
+            self.ctx.gd_update_device(updater_kind(updater), w_dev.shape[0], w_dev.data_ptr(), gsum.data_ptr(),
+                                      stepSize, iteration, regParam, out.data_ptr(),
+                                      out.data_ptr() + 8 * w_dev.shape[0], self.stream.cuda_stream)
+            regVal = float(out[-1:].cpu().numpy()[0])
+        return out[:-1], regVal
+
+
+def merge_gradient_sums(rows):
+    """Rows of {gradientSum[d], lossSum, count}, one a rank, added in row order: ((r0 + r1) + r2) + ..
+    (host arrays or device tensors)."""
+    total = rows[0] + 0.0
+    for r in range(1, len(rows)):
+        total = total + rows[r]
+    return total
+
 
 def merge_column_stats(h: np.ndarray, d: int) -> "ColumnStats":
     """Rows of {count, mean[d], m2[d], numNonzeros[d], max[d], min[d]} merged in row order with
