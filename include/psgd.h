@@ -317,6 +317,17 @@ int32_t psgd_gd_update_device(psgd_ctx* ctx, int32_t updater, int32_t d, const d
  * storage: 1 = f32 rows, 0 = f64 rows. */
 int32_t psgd_ctx_last_kernel(psgd_ctx* ctx);
 
+/* Diagnostics: the LDS row ring of the last chain launch, out4 = {R, MB, D, GS}: R row slots, MB
+ * 256-byte meta blocks (16 rows' labels and steps each), D rows the loader keeps in flight, GS
+ * Gram slots (the blocked kernels; else 0). Set by the kernels that stream rows through the ring
+ * (variants 100, 300, 700 and 800); zeros after a launch of any other kernel. The ring is the
+ * deepest that fits the per-workgroup LDS budget, 160 KiB / ceil(P / CUs) - 512 bytes rounded
+ * down to 256 for P chains, so that the chains spread evenly over the CUs; where that is less
+ * than the kernel's minimum ring (R = 6 per-sample, R = 16 blocked: rows of 8 KiB from P > CUs
+ * on) the launch takes the minimum ring and fewer chains share a CU. The ring only moves rows:
+ * the results do not depend on it. PSGD_EINVAL for a null ctx or out4. */
+int32_t psgd_ctx_last_ring(psgd_ctx* ctx, int32_t out4[4]);
+
 /* Diagnostics: device time of the last chain-kernel launch in milliseconds, from HIP events
  * recorded around it on the launch stream (waits for that launch to finish). */
 int32_t psgd_ctx_last_chain_ms(psgd_ctx* ctx, double* ms_out);

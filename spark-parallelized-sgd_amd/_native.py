@@ -25,7 +25,7 @@ EXPORTED = (
     "psgd_clear_partitions", "psgd_num_partitions", "psgd_run_epoch", "psgd_run_epoch_device",
     "psgd_fold_partials_device", "psgd_run_epoch_device_mirror", "psgd_fold_partials_device_mirror",
     "psgd_convergence_terms_device", "psgd_initial_regval",
-    "psgd_ctx_last_kernel", "psgd_ctx_last_chain_ms", "psgd_ctx_chain_launches", "psgd_ctx_chain_ms",
+    "psgd_ctx_last_kernel", "psgd_ctx_last_ring", "psgd_ctx_last_chain_ms", "psgd_ctx_chain_launches", "psgd_ctx_chain_ms",
     "psgd_vmm_stats", "psgd_reroll_stats", "psgd_libsvm_read", "psgd_libsvm_free",
     "psgd_sample_partition", "psgd_host_alloc", "psgd_host_free", "psgd_register_wait",
     "psgd_evaluate", "psgd_evaluate_device", "psgd_predict", "psgd_predict_device",
@@ -109,6 +109,7 @@ def lib():
             "psgd_convergence_terms_device": ([vp, C.c_int32, vp, vp, dp, vp], C.c_int32),
             "psgd_initial_regval": ([vp, P, C.c_int32, vp, dp], C.c_int32),
             "psgd_ctx_last_kernel": ([vp], C.c_int32),
+            "psgd_ctx_last_ring": ([vp, i32p], C.c_int32),
             "psgd_ctx_last_chain_ms": ([vp, dp], C.c_int32),
             "psgd_ctx_chain_launches": ([vp], C.c_int64),
             "psgd_ctx_chain_ms": ([vp, C.c_int64, dp], C.c_int32),
@@ -275,6 +276,13 @@ class Context:
 
     def last_kernel(self) -> int:
         return int(self._L.psgd_ctx_last_kernel(self.handle))
+
+    def last_ring(self):
+        """(R, MB, D, GS) of the LDS row ring of the last chain launch: row slots, meta blocks,
+        loader depth, Gram slots; zeros when the last kernel has no ring."""
+        out = (C.c_int32 * 4)()
+        check(self._L.psgd_ctx_last_ring(self.handle, out))
+        return tuple(int(v) for v in out)
 
     def last_chain_ms(self) -> float:
         """Device time of the last chain-kernel launch (HIP events on its stream)."""

@@ -732,27 +732,21 @@ int launch_margin_loss(const ChainLaunch& L, int n_chains, hipStream_t st) {
 // ------------------------------------------------------------------------------------------
 // Launcher.
 // ------------------------------------------------------------------------------------------
+// chain_block's ring: the two headers, the meta ring, one Gram slot per block and one spare, the
+// rows. A block never wraps (R a multiple of kBlk), and the loader needs two blocks: one for the
+// chain wave to hold while the stream fills the other.
+RingPlan block_ring_plan(int nv, bool conv, size_t budget) {
+    const size_t gslot = (size_t)(conv ? gram_slot32<true>() : gram_slot32<false>()) * 4;
+    return plan_ring(budget, sizeof(RingHeader) + sizeof(GramHeader), nv, gslot, kBlk, 2 * kBlk);
+}
+
 template <typename S, int GRAD, int UPD, int NV, bool CONV>
-static int launch_block(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st) {
-    constexpr int ROW = NV * 1024;
-    const size_t budget = lds > 0 ? lds : (size_t)64 * 1024;
-    const size_t fixed = sizeof(RingHeader) + sizeof(GramHeader);
-    const int D = loader_depth<NV>();
-    int R = 0, MB = 0, GS = 0;
-    auto bytes_for = [&](int r) {
-        const int mb = (r + kMetaRows - 1) / kMetaRows + 2;
-        const int gs = r / kBlk + 1;
-        return fixed + (size_t)mb * kMetaBlockBytes + (size_t)gs * gram_slot32<CONV>() * 4 + (size_t)r * ROW;
-    };
-    // a block never wraps (R multiple of kBlk); one block beyond the loader's depth keeps the
-    // stream going while the chain wave holds a block
-    R = (int)((budget - fixed) / ROW) / kBlk * kBlk;
-    while (R > 0 && bytes_for(R) > budget) R -= kBlk;
-    if (R < 2 * kBlk) return (int)hipErrorInvalidValue;  // LDS budget too small for this d
-    MB = (R + kMetaRows - 1) / kMetaRows + 2;
-    GS = R / kBlk + 1;
-    RingGeom g{R, MB, D, GS};
-    const size_t bytes = bytes_for(R);
+static int launch_block(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st,
+                        int* ring = nullptr) {
+    const RingPlan plan = block_ring_plan(NV, CONV, lds > 0 ? lds : (size_t)64 * 1024);
+    const RingGeom g = plan.g;
+    const size_t bytes = plan.bytes;
+    note_ring(ring, g);
     if (full) {
         auto k = chain_block<S, GRAD, UPD, NV, true, CONV>;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -774,41 +768,41 @@ static int launch_block(const ChainLaunch& L, const KParams& kp, bool full, size
 // Variant 300 + 40 (the per-sample break, tol > 0) + NV.
 template <typename S, int GRAD, int UPD, bool CONV>
 static int block_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld,
-                    size_t lds, hipStream_t st, int* variant) {
+                    size_t lds, hipStream_t st, int* variant, int* ring) {
     constexpr int VEC = 16 / sizeof(S);
     int nv = 1;
     while (nv * 64 * VEC < max_ld) nv *= 2;
     const bool full = min_ld >= (int64_t)nv * 64 * VEC;
     if (variant) *variant = 300 + (CONV ? 40 : 0) + nv;
     switch (nv) {
-    case 1: return launch_block<S, GRAD, UPD, 1, CONV>(L, kp, full, lds, st);
-    case 2: return launch_block<S, GRAD, UPD, 2, CONV>(L, kp, full, lds, st);
-    case 4: return launch_block<S, GRAD, UPD, 4, CONV>(L, kp, full, lds, st);
-    case 8: return launch_block<S, GRAD, UPD, 8, CONV>(L, kp, full, lds, st);
+    case 1: return launch_block<S, GRAD, UPD, 1, CONV>(L, kp, full, lds, st, ring);
+    case 2: return launch_block<S, GRAD, UPD, 2, CONV>(L, kp, full, lds, st, ring);
+    case 4: return launch_block<S, GRAD, UPD, 4, CONV>(L, kp, full, lds, st, ring);
+    case 8: return launch_block<S, GRAD, UPD, 8, CONV>(L, kp, full, lds, st, ring);
     default: return -3;
     }
 }
 
 template <typename S, int GRAD>
 static int block_upd(const ChainLaunch& L, const KParams& kp, int upd, int64_t min_ld,
-                     int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
+                     int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
     const bool conv = kp.tol > 0.0;   // the per-sample break: a template instance of its own
     if (upd == U_SIMPLE)
-        return conv ? block_nv<S, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant)
-                    : block_nv<S, GRAD, U_SIMPLE, false>(L, kp, min_ld, max_ld, lds, st, variant);
+        return conv ? block_nv<S, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
+                    : block_nv<S, GRAD, U_SIMPLE, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
     if (upd == U_SQUARED_L2)
-        return conv ? block_nv<S, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant)
-                    : block_nv<S, GRAD, U_SQUARED_L2, false>(L, kp, min_ld, max_ld, lds, st, variant);
+        return conv ? block_nv<S, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
+                    : block_nv<S, GRAD, U_SQUARED_L2, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
     return -3;
 }
 
 template <typename S>
 static int block_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, int64_t min_ld,
-                      int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
+                      int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
     switch (grad) {
-    case G_LOGISTIC: return block_upd<S, G_LOGISTIC>(L, kp, upd, min_ld, max_ld, lds, st, variant);
-    case G_LEAST_SQUARES: return block_upd<S, G_LEAST_SQUARES>(L, kp, upd, min_ld, max_ld, lds, st, variant);
-    case G_HINGE: return block_upd<S, G_HINGE>(L, kp, upd, min_ld, max_ld, lds, st, variant);
+    case G_LOGISTIC: return block_upd<S, G_LOGISTIC>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
+    case G_LEAST_SQUARES: return block_upd<S, G_LEAST_SQUARES>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
+    case G_HINGE: return block_upd<S, G_HINGE>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
     default: return -3;
     }
 }
@@ -828,12 +822,12 @@ bool block_path_applies(int layout, int compute, int updater, bool check_conv, i
 
 int launch_block_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
                         int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                        hipStream_t stream, int* kernel_variant) {
+                        hipStream_t stream, int* kernel_variant, int* ring) {
     if (kp.n_chains <= 0) return 0;
     const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
     if (storage == 1)
-        return block_grad<float>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant);
-    return block_grad<double>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant);
+        return block_grad<float>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
+    return block_grad<double>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
 }
 
 #endif  // PSGD_NO_DISPATCH

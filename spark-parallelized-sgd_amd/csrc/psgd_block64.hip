@@ -962,24 +962,23 @@ void chain_block64(ChainLaunch L, KParams kp, RingGeom geom) {
 // ------------------------------------------------------------------------------------------
 // Launcher.
 // ------------------------------------------------------------------------------------------
+// chain_block64's ring: the fixed area (headers and the chain waves' exchange), the meta ring, one
+// Gram slot per block and one spare (two sub-slots each where the Gram waves split the features,
+// gram_fsplit64), the rows. R a multiple of kB, at least two blocks, as for chain_block; the
+// number of chain waves does not enter.
+RingPlan block64_ring_plan(int nv, bool conv, size_t budget) {
+    const bool fs = PSGD_B64_FSPLIT_NV > 0 && nv >= PSGD_B64_FSPLIT_NV && nv >= 2;   // gram_fsplit64<NV>()
+    const size_t gslot = (size_t)(conv ? gram_slot64<true>() : gram_slot64<false>()) * 8 * (fs ? 2 : 1);
+    return plan_ring(budget, kFixed64, nv, gslot, kB, 2 * kB);
+}
+
 template <typename S, int GRAD, int UPD, int NV, int H, bool CONV>
-static int launch_block64(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st) {
-    constexpr int ROW = NV * 1024;
-    const size_t budget = lds > 0 ? lds : (size_t)64 * 1024;
-    const int D = loader_depth<NV>();
-    auto bytes_for = [&](int r) {
-        const int mb = (r + kMetaRows - 1) / kMetaRows + 2;
-        const int gs = r / kB + 1;
-        return kFixed64 + (size_t)mb * kMetaBlockBytes +
-               (size_t)gs * gram_slot64<CONV>() * 8 * (gram_fsplit64<NV>() ? 2 : 1) + (size_t)r * ROW;
-    };
-    int R = (int)((budget - kFixed64) / ROW) / kB * kB;
-    while (R > 0 && bytes_for(R) > budget) R -= kB;
-    if (R < 2 * kB) return (int)hipErrorInvalidValue;   // LDS budget too small for this d
-    const int MB = (R + kMetaRows - 1) / kMetaRows + 2;
-    const int GS = R / kB + 1;
-    RingGeom g{R, MB, D, GS};
-    const size_t bytes = bytes_for(R);
+static int launch_block64(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st,
+                          int* ring = nullptr) {
+    const RingPlan plan = block64_ring_plan(NV, CONV, lds > 0 ? lds : (size_t)64 * 1024);
+    const RingGeom g = plan.g;
+    const size_t bytes = plan.bytes;
+    note_ring(ring, g);
     const dim3 threads(64 * (3 + H));
     if (full) {
         auto k = chain_block64<S, GRAD, UPD, NV, true, H, CONV>;
@@ -1003,7 +1002,7 @@ static int launch_block64(const ChainLaunch& L, const KParams& kp, bool full, si
 // 10 (H - 1) + NV.
 template <typename S, int GRAD, int UPD, bool CONV>
 static int block64_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld,
-                      size_t lds, hipStream_t st, int* variant) {
+                      size_t lds, hipStream_t st, int* variant, int* ring) {
     constexpr int VEC = 16 / sizeof(S);
     static const bool one_wave = [] {
         const char* e = getenv("PSGD_B64_WAVES");
@@ -1016,41 +1015,41 @@ static int block64_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, i
     if (variant) *variant = 700 + (CONV ? 40 : 0) + 10 * (H - 1) + nv;
     if (H == 1) {
         switch (nv) {
-        case 1: return launch_block64<S, GRAD, UPD, 1, 1, CONV>(L, kp, full, lds, st);
-        case 2: return launch_block64<S, GRAD, UPD, 2, 1, CONV>(L, kp, full, lds, st);
-        case 4: return launch_block64<S, GRAD, UPD, 4, 1, CONV>(L, kp, full, lds, st);
+        case 1: return launch_block64<S, GRAD, UPD, 1, 1, CONV>(L, kp, full, lds, st, ring);
+        case 2: return launch_block64<S, GRAD, UPD, 2, 1, CONV>(L, kp, full, lds, st, ring);
+        case 4: return launch_block64<S, GRAD, UPD, 4, 1, CONV>(L, kp, full, lds, st, ring);
         default: return -3;
         }
     }
     switch (nv) {
-    case 2: return launch_block64<S, GRAD, UPD, 2, 2, CONV>(L, kp, full, lds, st);
-    case 4: return launch_block64<S, GRAD, UPD, 4, 2, CONV>(L, kp, full, lds, st);
-    case 8: return launch_block64<S, GRAD, UPD, 8, 2, CONV>(L, kp, full, lds, st);
+    case 2: return launch_block64<S, GRAD, UPD, 2, 2, CONV>(L, kp, full, lds, st, ring);
+    case 4: return launch_block64<S, GRAD, UPD, 4, 2, CONV>(L, kp, full, lds, st, ring);
+    case 8: return launch_block64<S, GRAD, UPD, 8, 2, CONV>(L, kp, full, lds, st, ring);
     default: return -3;
     }
 }
 
 template <typename S, int GRAD>
 static int block64_upd(const ChainLaunch& L, const KParams& kp, int upd, int64_t min_ld,
-                       int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
+                       int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
     // the per-sample break (tol > 0, PSGD.scala:262) is a template instance of its own
     const bool conv = kp.tol > 0.0;
     if (upd == U_SIMPLE)
-        return conv ? block64_nv<S, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant)
-                    : block64_nv<S, GRAD, U_SIMPLE, false>(L, kp, min_ld, max_ld, lds, st, variant);
+        return conv ? block64_nv<S, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
+                    : block64_nv<S, GRAD, U_SIMPLE, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
     if (upd == U_SQUARED_L2)
-        return conv ? block64_nv<S, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant)
-                    : block64_nv<S, GRAD, U_SQUARED_L2, false>(L, kp, min_ld, max_ld, lds, st, variant);
+        return conv ? block64_nv<S, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
+                    : block64_nv<S, GRAD, U_SQUARED_L2, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
     return -3;
 }
 
 template <typename S>
 static int block64_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, int64_t min_ld,
-                        int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
+                        int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
     switch (grad) {
-    case G_LOGISTIC: return block64_upd<S, G_LOGISTIC>(L, kp, upd, min_ld, max_ld, lds, st, variant);
-    case G_LEAST_SQUARES: return block64_upd<S, G_LEAST_SQUARES>(L, kp, upd, min_ld, max_ld, lds, st, variant);
-    case G_HINGE: return block64_upd<S, G_HINGE>(L, kp, upd, min_ld, max_ld, lds, st, variant);
+    case G_LOGISTIC: return block64_upd<S, G_LOGISTIC>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
+    case G_LEAST_SQUARES: return block64_upd<S, G_LEAST_SQUARES>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
+    case G_HINGE: return block64_upd<S, G_HINGE>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
     default: return -3;
     }
 }
@@ -1071,13 +1070,13 @@ bool block64_path_applies(int layout, int compute, int updater, bool check_conv,
 
 int launch_block64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
                           int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                          hipStream_t stream, int* kernel_variant) {
+                          hipStream_t stream, int* kernel_variant, int* ring) {
     if (kp.n_chains <= 0) return 0;
     if (gradient == G_LOGISTIC && !L.zbuf64) return (int)hipErrorInvalidValue;
     const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
     if (storage == 1)
-        return block64_grad<float>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant);
-    return block64_grad<double>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant);
+        return block64_grad<float>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
+    return block64_grad<double>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
 }
 
 #endif  // PSGD_NO_DISPATCH

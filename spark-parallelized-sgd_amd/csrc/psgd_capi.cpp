@@ -423,6 +423,7 @@ struct psgd_ctx {
     double steps_value = NAN;
     int64_t steps_n = 0;
     int32_t last_variant = 0;
+    int last_ring[4] = {0, 0, 0, 0};   // {R, MB, D, GS} of the last ring-kernel launch (psgd_ctx_last_ring)
     // HIP events around the last kChainEvents chain-kernel launches, launch k in slot
     // k % kChainEvents (psgd_ctx_last_chain_ms, psgd_ctx_chain_ms): a caller that keeps several
     // epochs in flight reads each launch's time after it has enqueued later ones
@@ -750,7 +751,9 @@ int32_t ensure_steps(psgd_ctx* ctx, double step, int64_t n, hipStream_t st) {
 
 // Per-workgroup LDS budget for the dense chain kernel's row ring: as deep a ring as possible
 // while floor(160 KiB / budget) chain workgroups fit per CU, so P chains spread evenly over
-// the CUs (one per CU for P <= #CUs). PSGD_LDS_BUDGET overrides (bytes).
+// the CUs (one per CU for P <= #CUs). PSGD_LDS_BUDGET overrides (bytes). A budget below a
+// kernel's minimum ring (many chains per CU, wide rows) is raised to it by the launchers
+// (plan_ring, psgd_device.h): fewer chains are then co-resident than the spread asked for.
 int lds_spread_bytes(const psgd_ctx* ctx, size_t P) {
     const char* env = getenv("PSGD_LDS_BUDGET");
     if (env) return std::max(0, atoi(env));
@@ -1381,7 +1384,7 @@ static int32_t run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const 
                                     params->compute_dtype == PSGD_F32 ? 1 : 0, params->gradient,
                                     params->updater, conv, min_ld, max_ld,
                                     lds_spread_bytes(ctx, (size_t)P), st, &ctx->last_variant, max_nnz,
-                                    &weights_in);
+                                    &weights_in, ctx->last_ring);
         HIP_TRY(hipEventRecord(ctx->ev_end[ek], st));
         if (e == 0) ++ctx->chain_launches;
         if (L.stamps) {   // PSGD_STAMPS=1: per-chain cycle counters of the CSR fp32 kernels (stderr)
@@ -2058,6 +2061,12 @@ int32_t psgd_sample_partition(int32_t device, int64_t seed, int64_t n, double fr
 }
 
 int32_t psgd_ctx_last_kernel(psgd_ctx* ctx) { return ctx ? ctx->last_variant : 0; }
+
+int32_t psgd_ctx_last_ring(psgd_ctx* ctx, int32_t out4[4]) {
+    if (!ctx || !out4) return fail(PSGD_EINVAL, "null argument");
+    for (int k = 0; k < 4; ++k) out4[k] = ctx->last_ring[k];
+    return PSGD_OK;
+}
 
 int32_t psgd_ctx_chain_ms(psgd_ctx* ctx, int64_t launch, double* ms_out) {
     if (!ctx || !ms_out) return fail(PSGD_EINVAL, "ctx/ms_out is null");

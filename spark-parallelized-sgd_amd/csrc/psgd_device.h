@@ -474,9 +474,55 @@ __device__ __forceinline__ void lds_store_u32_asm(unsigned* p, unsigned v) {
 #define PSGD_LOAD_AUX 2
 #endif
 
+__host__ __device__ constexpr int loader_depth_of(int nv) {
+    return nv == 1 ? 56 : nv == 2 ? 28 : nv == 4 ? 14 : 7;   // <= 56 instructions in vmcnt
+}
 template <int NV>
 __host__ __device__ constexpr int loader_depth() {
-    return NV == 1 ? 56 : NV == 2 ? 28 : NV == 4 ? 14 : 7;   // <= 56 instructions in vmcnt
+    return loader_depth_of(NV);
+}
+
+// The ring a launcher requests for a per-workgroup LDS budget (host side; every dense chain
+// kernel's launcher goes through it, and ring_geometry exports it for the tests). The LDS request
+// is `fixed` bytes of headers, MB = ceil(R / 16) + 2 meta blocks, GS = R / blk + 1 Gram slots of
+// gslot_bytes each (the blocked kernels; gslot_bytes = 0: no Gram ring, GS = 0) and R rows of
+// NV KiB. R is the largest multiple of blk whose request fits the budget. A budget below the
+// request of the kernel's minimum ring (min_rows: PUB + 2 for the per-sample kernels, two blocks
+// for the blocked ones) gets the minimum ring all the same: with many chains per CU the even
+// spread of the LDS (lds_spread_bytes) asks for less than a wide row's ring can be, and fewer
+// co-resident chains are the price of running at all.
+struct RingPlan {
+    RingGeom g;
+    size_t bytes;   // the launch's dynamic LDS
+};
+inline RingPlan plan_ring(size_t budget, size_t fixed, int nv, size_t gslot_bytes, int blk, int min_rows) {
+    const size_t row = (size_t)nv * 1024;
+    auto geom = [&](int r) {
+        return RingGeom{r, (r + kMetaRows - 1) / kMetaRows + 2, loader_depth_of(nv),
+                        gslot_bytes ? r / blk + 1 : 0};
+    };
+    auto bytes_for = [&](int r) {
+        const RingGeom g = geom(r);
+        return fixed + (size_t)g.meta_blocks * kMetaBlockBytes + (size_t)g.gslots * gslot_bytes + (size_t)r * row;
+    };
+    int r = budget > fixed ? (int)((budget - fixed) / row) / blk * blk : 0;
+    while (r > min_rows && bytes_for(r) > budget) r -= blk;
+    if (r < min_rows) r = min_rows;
+    return RingPlan{geom(r), bytes_for(r)};
+}
+// One per kernel family, next to its launcher. compute: 0 = f64, 1 = f32 (chain_split's exchange
+// area); conv: the per-sample break's instances (wider exchange / Gram slots).
+RingPlan dense_ring_plan(int nv, size_t budget);
+RingPlan split_ring_plan(int nv, int compute, bool conv, size_t budget);
+RingPlan block_ring_plan(int nv, bool conv, size_t budget);
+RingPlan block64_ring_plan(int nv, bool conv, size_t budget);
+// {R, MB, D, GS} of a launch, for psgd_ctx_last_ring (ring: nullable)
+inline void note_ring(int* ring, const RingGeom& g) {
+    if (!ring) return;
+    ring[0] = g.rows;
+    ring[1] = g.meta_blocks;
+    ring[2] = g.depth;
+    ring[3] = g.gslots;
 }
 
 __device__ __forceinline__ void lds_store_u32_nowait(unsigned* p, unsigned v) {

@@ -87,21 +87,31 @@ struct ChainLaunch {
 int launch_chains(const ChainLaunch& L, const KParams& kp, int layout, int storage, int compute,
                   int gradient, int updater, bool check_conv, int64_t min_ld, int64_t max_ld,
                   int lds_spread, hipStream_t stream, int* kernel_variant, int64_t max_nnz = 0,
-                  int* weights_in = nullptr);
+                  int* weights_in = nullptr, int* ring = nullptr);
+// *ring (nullable, 4 ints): {R, MB, D, GS} of the LDS ring the launch gave chain_dense /
+// chain_split / chain_block / chain_block64; zeros when another kernel ran.
+// The same geometry without a launch (host only; the tests call it through its mangled name):
+// family kRing*, nv row vectors (1, 2, 4, 8; chain_split from 2), compute 0 = f64 / 1 = f32
+// (chain_split only), conv = the tol > 0 instances, budget = the per-workgroup LDS budget in
+// bytes (<= 0: the launchers' 64 KiB default). out5 = {R, MB, D, GS, LDS bytes of the launch}.
+// A budget below the family's minimum ring (6 rows; 16 for the blocked kernels) gets that
+// minimum ring. Returns 0, or -1 for a family / nv that does not exist.
+enum { kRingDense = 0, kRingSplit = 1, kRingBlock = 2, kRingBlock64 = 3 };
+int ring_geometry(int family, int nv, int compute, bool conv, int64_t budget, int32_t* out5);
 // The blocked fp32 kernel (psgd_block.hip): dense rows, Simple/SquaredL2, no per-sample
 // convergence test. launch_block_chains returns -3 when it does not apply.
 bool block_path_applies(int layout, int compute, int updater, bool check_conv, int storage,
                         int64_t max_ld);
 int launch_block_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
                         int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                        hipStream_t stream, int* kernel_variant);
+                        hipStream_t stream, int* kernel_variant, int* ring = nullptr);
 // The blocked fp64 kernel (psgd_block64.hip): dense rows, Simple/SquaredL2, fp64 compute, no
 // per-sample convergence test (the parity mode's throughput kernel). -3 when it does not apply.
 bool block64_path_applies(int layout, int compute, int updater, bool check_conv, int storage,
                           int64_t max_ld);
 int launch_block64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
                           int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                          hipStream_t stream, int* kernel_variant);
+                          hipStream_t stream, int* kernel_variant, int* ring = nullptr);
 // lossSum of fp64 Logistic chains from the per-row dots in L.zbuf64 (psgd_kernels.hip).
 int launch_logistic_loss64(const ChainLaunch& L, int n_chains, hipStream_t stream);
 // lossSum of fp32 Logistic chains from the per-row margins in L.zbuf (psgd_block.hip).

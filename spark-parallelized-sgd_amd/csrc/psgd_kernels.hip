@@ -895,27 +895,39 @@ __global__ void steps_kernel(double step, int64_t n, double* __restrict__ steps)
 // ------------------------------------------------------------------------------------------
 // Launchers / dispatch.
 // ------------------------------------------------------------------------------------------
+// chain_dense's ring: the header, then the meta and row rings; at least PUB + 2 = 6 rows.
+RingPlan dense_ring_plan(int nv, size_t budget) {
+    return plan_ring(budget, sizeof(RingHeader), nv, 0, 1, 6);
+}
+
+int ring_geometry(int family, int nv, int compute, bool conv, int64_t budget, int32_t* out5) {
+    if (!out5 || (nv != 1 && nv != 2 && nv != 4 && nv != 8)) return -1;
+    const size_t b = budget > 0 ? (size_t)budget : (size_t)64 * 1024;   // as the launchers
+    RingPlan p;
+    switch (family) {
+    case kRingDense: p = dense_ring_plan(nv, b); break;
+    case kRingSplit:
+        if (nv < 2) return -1;
+        p = split_ring_plan(nv, compute, conv, b);
+        break;
+    case kRingBlock: p = block_ring_plan(nv, conv, b); break;
+    case kRingBlock64: p = block64_ring_plan(nv, conv, b); break;
+    default: return -1;
+    }
+    note_ring(out5, p.g);
+    out5[4] = (int32_t)p.bytes;
+    return 0;
+}
+
 template <typename S, typename T, int GRAD, int UPD, bool CONV, int NV>
-static int launch_reg(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st) {
-    // Ring geometry from the per-workgroup LDS budget (`lds`: chosen by the host so that the
-    // chains spread evenly over the CUs). D rows stay in flight beyond the newest published row
-    // (vmcnt holds at most 63 instructions, NV per row); R - D >= 8 slots stay published or
-    // free so neither wave can wait on the other forever.
-    constexpr int ROW = NV * 1024;
+static int launch_reg(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st, int* ring) {
     // Ring geometry from the per-workgroup LDS budget (`lds`: chosen by the host so that the
     // chains spread evenly over the CUs); the consumer reads rows t and t+1, the loader keeps
     // loader_depth rows in flight and drains before it blocks on a full ring.
-    const size_t budget = lds > 0 ? lds : (size_t)64 * 1024;
-    const int D = loader_depth<NV>();
-    int R = (int)((budget - sizeof(RingHeader) - 3 * kMetaBlockBytes) / ROW);
-    int MB = (R + kMetaRows - 1) / kMetaRows + 2;
-    while (R > 0 && sizeof(RingHeader) + (size_t)MB * kMetaBlockBytes + (size_t)R * ROW > budget) {
-        --R;
-        MB = (R + kMetaRows - 1) / kMetaRows + 2;
-    }
-    if (R < 6) return (int)hipErrorInvalidValue;  // LDS budget too small for this d (R >= PUB + 2)
-    RingGeom g{R, MB, D, 0};
-    const size_t bytes = sizeof(RingHeader) + (size_t)MB * kMetaBlockBytes + (size_t)R * ROW;
+    const RingPlan plan = dense_ring_plan(NV, lds > 0 ? lds : (size_t)64 * 1024);
+    const RingGeom g = plan.g;
+    const size_t bytes = plan.bytes;
+    note_ring(ring, g);
     if (full) {
         auto k = chain_dense<S, T, GRAD, UPD, CONV, NV, true>;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -940,7 +952,7 @@ int launch_logistic_loss64(const ChainLaunch& L, int n_chains, hipStream_t st) {
 
 template <typename S, typename T, int GRAD, int UPD, bool CONV>
 static int dispatch_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld,
-                       size_t lds, hipStream_t st, int* variant) {
+                       size_t lds, hipStream_t st, int* variant, int* ring) {
     constexpr int VEC = 16 / sizeof(S);
     int nv = 1;
     while (nv * 64 * VEC < max_ld) nv *= 2;
@@ -950,11 +962,11 @@ static int dispatch_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, 
     // fp64 AdaGrad / Adam hold at most 16 doubles per lane (dispatch_layout): no NV past that
     constexpr int NVMAX = (sizeof(T) == 8 && UPD >= U_ADAGRAD) ? 16 / VEC : 8;
     switch (nv) {
-    case 1: return launch_reg<S, T, GRAD, UPD, CONV, 1>(L, kp, full, lds, st);
-    case 2: return launch_reg<S, T, GRAD, UPD, CONV, 2>(L, kp, full, lds, st);
-    case 4: return launch_reg<S, T, GRAD, UPD, CONV, 4>(L, kp, full, lds, st);
+    case 1: return launch_reg<S, T, GRAD, UPD, CONV, 1>(L, kp, full, lds, st, ring);
+    case 2: return launch_reg<S, T, GRAD, UPD, CONV, 2>(L, kp, full, lds, st, ring);
+    case 4: return launch_reg<S, T, GRAD, UPD, CONV, 4>(L, kp, full, lds, st, ring);
     case 8:
-        if constexpr (NVMAX >= 8) return launch_reg<S, T, GRAD, UPD, CONV, 8>(L, kp, full, lds, st);
+        if constexpr (NVMAX >= 8) return launch_reg<S, T, GRAD, UPD, CONV, 8>(L, kp, full, lds, st, ring);
         return -1;
     default: return -1;
     }
@@ -970,21 +982,21 @@ static int launch_gen(const ChainLaunch& L, const KParams& kp, hipStream_t st, i
 
 template <typename S, int GRAD, int UPD, bool CONV>
 static int dispatch_layout(const ChainLaunch& L, const KParams& kp, int layout, int compute,
-                           int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
+                           int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
     constexpr int VEC = 16 / sizeof(S);
     if constexpr (UPD <= U_L1) {
         if (layout == kDense && max_ld <= 8 * 64 * VEC) {
-            if (compute == 1) return dispatch_nv<S, float, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant);
-            return dispatch_nv<S, double, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant);
+            if (compute == 1) return dispatch_nv<S, float, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
+            return dispatch_nv<S, double, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
         }
     } else {
         // AdaGrad / Adam: weights and status in registers. fp32: up to 8 row vectors per lane;
         // fp64 (the parity mode): up to 16 doubles per lane (weights, status and two row buffers
         // are 5 x 16 doubles = 160 VGPRs), d <= 1,024; past that chain_general, status in HBM
         if (layout == kDense && compute == 1 && max_ld <= 8 * 64 * VEC)
-            return dispatch_nv<S, float, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant);
+            return dispatch_nv<S, float, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
         if (layout == kDense && compute == 0 && max_ld <= 16 * 64)
-            return dispatch_nv<S, double, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant);
+            return dispatch_nv<S, double, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
     }
     if (layout == kDense) return launch_gen<S, kDense, GRAD, UPD, CONV>(L, kp, st, variant);
     return launch_gen<S, kCsr, GRAD, UPD, CONV>(L, kp, st, variant);
@@ -992,20 +1004,20 @@ static int dispatch_layout(const ChainLaunch& L, const KParams& kp, int layout, 
 
 template <typename S, int GRAD, int UPD>
 static int dispatch_conv(const ChainLaunch& L, const KParams& kp, int layout, int compute,
-                         bool conv, int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
-    if (conv) return dispatch_layout<S, GRAD, UPD, true>(L, kp, layout, compute, min_ld, max_ld, lds, st, variant);
-    return dispatch_layout<S, GRAD, UPD, false>(L, kp, layout, compute, min_ld, max_ld, lds, st, variant);
+                         bool conv, int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
+    if (conv) return dispatch_layout<S, GRAD, UPD, true>(L, kp, layout, compute, min_ld, max_ld, lds, st, variant, ring);
+    return dispatch_layout<S, GRAD, UPD, false>(L, kp, layout, compute, min_ld, max_ld, lds, st, variant, ring);
 }
 
 template <typename S, int GRAD>
 static int dispatch_upd(const ChainLaunch& L, const KParams& kp, int layout, int compute, int upd,
-                        bool conv, int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
+                        bool conv, int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
     switch (upd) {
-    case U_SIMPLE: return dispatch_conv<S, GRAD, U_SIMPLE>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant);
-    case U_SQUARED_L2: return dispatch_conv<S, GRAD, U_SQUARED_L2>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant);
-    case U_L1: return dispatch_conv<S, GRAD, U_L1>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant);
-    case U_ADAGRAD: return dispatch_conv<S, GRAD, U_ADAGRAD>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant);
-    case U_ADAM: return dispatch_conv<S, GRAD, U_ADAM>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant);
+    case U_SIMPLE: return dispatch_conv<S, GRAD, U_SIMPLE>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
+    case U_SQUARED_L2: return dispatch_conv<S, GRAD, U_SQUARED_L2>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
+    case U_L1: return dispatch_conv<S, GRAD, U_L1>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
+    case U_ADAGRAD: return dispatch_conv<S, GRAD, U_ADAGRAD>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
+    case U_ADAM: return dispatch_conv<S, GRAD, U_ADAM>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
     default: return -1;
     }
 }
@@ -1013,11 +1025,11 @@ static int dispatch_upd(const ChainLaunch& L, const KParams& kp, int layout, int
 template <typename S>
 static int dispatch_grad(const ChainLaunch& L, const KParams& kp, int layout, int compute, int grad,
                          int upd, bool conv, int64_t min_ld, int64_t max_ld, size_t lds,
-                         hipStream_t st, int* variant) {
+                         hipStream_t st, int* variant, int* ring) {
     switch (grad) {
-    case G_LOGISTIC: return dispatch_upd<S, G_LOGISTIC>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant);
-    case G_LEAST_SQUARES: return dispatch_upd<S, G_LEAST_SQUARES>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant);
-    case G_HINGE: return dispatch_upd<S, G_HINGE>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant);
+    case G_LOGISTIC: return dispatch_upd<S, G_LOGISTIC>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant, ring);
+    case G_LEAST_SQUARES: return dispatch_upd<S, G_LEAST_SQUARES>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant, ring);
+    case G_HINGE: return dispatch_upd<S, G_HINGE>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant, ring);
     default: return -1;
     }
 }
@@ -1031,18 +1043,19 @@ bool per_sample_forced() {
 int launch_chains(const ChainLaunch& L, const KParams& kp, int layout, int storage, int compute,
                   int gradient, int updater, bool check_conv, int64_t min_ld, int64_t max_ld,
                   int lds_spread, hipStream_t stream, int* kernel_variant, int64_t max_nnz,
-                  int* weights_in) {
+                  int* weights_in, int* ring) {
     if (weights_in) *weights_in = kWeightsOut;
+    note_ring(ring, RingGeom{0, 0, 0, 0});   // stays zero unless a ring kernel launches
     if (kp.n_chains <= 0) return 0;
     if (kp.nc > 0)   // LogisticGradient(numClasses > 2)
         return launch_multinomial_chains(L, kp, layout, storage, updater, check_conv, stream, kernel_variant);
     const bool per_sample = per_sample_forced();
     if (!per_sample && block64_path_applies(layout, compute, updater, check_conv, storage, max_ld))
         return launch_block64_chains(L, kp, storage, gradient, updater, min_ld, max_ld, lds_spread,
-                                     stream, kernel_variant);
+                                     stream, kernel_variant, ring);
     if (!per_sample && block_path_applies(layout, compute, updater, check_conv, storage, max_ld))
         return launch_block_chains(L, kp, storage, gradient, updater, min_ld, max_ld, lds_spread,
-                                   stream, kernel_variant);
+                                   stream, kernel_variant, ring);
     if (!per_sample && sparse_path_applies(layout, compute, updater, check_conv)) {
         if (weights_in) *weights_in = kWeightsF32;
         const int e = launch_sparse_chains(L, kp, storage, gradient, updater, max_nnz, stream, kernel_variant);
@@ -1064,15 +1077,15 @@ int launch_chains(const ChainLaunch& L, const KParams& kp, int layout, int stora
     }
     if (!per_sample && split_path_applies(layout, updater, check_conv, storage, max_ld)) {
         const int e = launch_split_chains(L, kp, storage, compute, gradient, updater, min_ld, max_ld,
-                                          lds_spread, stream, kernel_variant);
+                                          lds_spread, stream, kernel_variant, ring);
         if (e != -3) return e;
     }
     const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
     if (storage == 1)
         return dispatch_grad<float>(L, kp, layout, compute, gradient, updater, check_conv, min_ld,
-                                    max_ld, lds, stream, kernel_variant);
+                                    max_ld, lds, stream, kernel_variant, ring);
     return dispatch_grad<double>(L, kp, layout, compute, gradient, updater, check_conv, min_ld,
-                                 max_ld, lds, stream, kernel_variant);
+                                 max_ld, lds, stream, kernel_variant, ring);
 }
 
 int launch_fold(const double* w, int64_t w_stride, const double* rv, const double* loss,

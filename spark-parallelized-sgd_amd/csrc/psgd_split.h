@@ -13,6 +13,6 @@ bool split_path_applies(int layout, int updater, bool check_conv, int storage, i
 // Kernel variant 800 + 10 H + NV (H compute waves, NV 1-KiB row vectors). -3 when it does not apply.
 int launch_split_chains(const ChainLaunch& L, const KParams& kp, int storage, int compute, int gradient,
                         int updater, int64_t min_ld, int64_t max_ld, int lds_spread, hipStream_t stream,
-                        int* kernel_variant);
+                        int* kernel_variant, int* ring = nullptr);
 
 }  // namespace psgd

@@ -99,9 +99,12 @@ constexpr unsigned kStopError = 1u, kStopConverged = 2u;
 
 // fixed LDS area: [RingHeader 16 B][exchange 2 x H x W u64 (W words per wave and sample)]
 // [SIMD ids of the H + 1 waves]
+constexpr size_t split_fixed_bytes_of(int h, int pc) {
+    return (sizeof(RingHeader) + 2 * h * pc * 8 + (h + 1) * 4 + 15) / 16 * 16;
+}
 template <int H, int PC>
 constexpr size_t split_fixed_bytes() {
-    return (sizeof(RingHeader) + 2 * H * PC * 8 + (H + 1) * 4 + 15) / 16 * 16;
+    return split_fixed_bytes_of(H, PC);
 }
 
 }  // namespace
@@ -668,27 +671,30 @@ int split_nv(int64_t max_ld) {
     return nv;
 }
 
+}  // namespace
+
+// chain_split's ring: the fixed area of H = min(NV, PSGD_SPLIT_HMAX) compute waves exchanging
+// sizeof(T) / 4 (x 3 with the per-sample break) words a sample, then the meta and row rings; at
+// least PUB + 2 = 6 rows.
+RingPlan split_ring_plan(int nv, int compute, bool conv, size_t budget) {
+    const int h = nv < PSGD_SPLIT_HMAX ? nv : PSGD_SPLIT_HMAX;
+    const int pc = (compute == 1 ? 1 : 2) * (conv ? 3 : 1);   // 32-bit words per wave and sample
+    return plan_ring(budget, split_fixed_bytes_of(h, pc), nv, 0, 1, 6);
+}
+
+namespace {
+
 template <typename S, typename T, int GRAD, int UPD, bool CONV, int NV>
-int launch_split(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st) {
+int launch_split(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st, int* ring) {
     constexpr int H = NV < PSGD_SPLIT_HMAX ? NV : PSGD_SPLIT_HMAX;
-    constexpr int PC = sizeof(T) / 4 * (CONV ? 3 : 1);   // 32-bit words per wave and sample
-    constexpr int ROW = NV * 1024;
-    constexpr size_t FIX = split_fixed_bytes<H, PC>();
-    const size_t budget = lds > 0 ? lds : (size_t)64 * 1024;
-    const int D = loader_depth<NV>();
-    int R = (int)((budget - FIX - 3 * kMetaBlockBytes) / ROW);
-    int MB = (R + kMetaRows - 1) / kMetaRows + 2;
-    while (R > 0 && FIX + (size_t)MB * kMetaBlockBytes + (size_t)R * ROW > budget) {
-        --R;
-        MB = (R + kMetaRows - 1) / kMetaRows + 2;
-    }
-    if (R < 6) return (int)hipErrorInvalidValue;   // the ring needs >= PUB + 2 slots
+    const RingPlan plan = split_ring_plan(NV, sizeof(T) == 8 ? 0 : 1, CONV, lds > 0 ? lds : (size_t)64 * 1024);
     if constexpr (GRAD == G_LOGISTIC) {
         // the rows' margins / dots, summed into the loss after the chain
         if (sizeof(T) == 8 ? !L.zbuf64 : !L.zbuf) return (int)hipErrorInvalidValue;
     }
-    RingGeom g{R, MB, D, 0};
-    const size_t bytes = FIX + (size_t)MB * kMetaBlockBytes + (size_t)R * ROW;
+    const RingGeom g = plan.g;
+    const size_t bytes = plan.bytes;
+    note_ring(ring, g);
     auto k = full ? chain_split<S, T, GRAD, UPD, CONV, NV, true, H> : chain_split<S, T, GRAD, UPD, CONV, NV, false, H>;
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(64 * (H + 1)), bytes, st, L, kp, g);
@@ -703,50 +709,50 @@ int launch_split(const ChainLaunch& L, const KParams& kp, bool full, size_t lds,
 
 template <typename S, typename T, int GRAD, int UPD, bool CONV>
 int split_dispatch_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld, size_t lds,
-                      hipStream_t st, int* variant) {
+                      hipStream_t st, int* variant, int* ring) {
     constexpr int VEC = 16 / sizeof(S);
     const int nv = split_nv<S>(max_ld);
     const bool full = min_ld >= (int64_t)nv * 64 * VEC;
     if (variant) *variant = 800 + 10 * (nv < PSGD_SPLIT_HMAX ? nv : PSGD_SPLIT_HMAX) + nv;
     switch (nv) {
-    case 2: return launch_split<S, T, GRAD, UPD, CONV, 2>(L, kp, full, lds, st);
-    case 4: return launch_split<S, T, GRAD, UPD, CONV, 4>(L, kp, full, lds, st);
-    case 8: return launch_split<S, T, GRAD, UPD, CONV, 8>(L, kp, full, lds, st);
+    case 2: return launch_split<S, T, GRAD, UPD, CONV, 2>(L, kp, full, lds, st, ring);
+    case 4: return launch_split<S, T, GRAD, UPD, CONV, 4>(L, kp, full, lds, st, ring);
+    case 8: return launch_split<S, T, GRAD, UPD, CONV, 8>(L, kp, full, lds, st, ring);
     default: return -3;
     }
 }
 
 template <typename S, typename T, int GRAD, bool CONV>
 int split_dispatch_conv(const ChainLaunch& L, const KParams& kp, int updater, int64_t min_ld, int64_t max_ld,
-                        size_t lds, hipStream_t st, int* variant) {
+                        size_t lds, hipStream_t st, int* variant, int* ring) {
     switch (updater) {
-    case U_ADAGRAD: return split_dispatch_nv<S, T, GRAD, U_ADAGRAD, CONV>(L, kp, min_ld, max_ld, lds, st, variant);
-    case U_ADAM: return split_dispatch_nv<S, T, GRAD, U_ADAM, CONV>(L, kp, min_ld, max_ld, lds, st, variant);
-    case U_L1: return split_dispatch_nv<S, T, GRAD, U_L1, CONV>(L, kp, min_ld, max_ld, lds, st, variant);
+    case U_ADAGRAD: return split_dispatch_nv<S, T, GRAD, U_ADAGRAD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
+    case U_ADAM: return split_dispatch_nv<S, T, GRAD, U_ADAM, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
+    case U_L1: return split_dispatch_nv<S, T, GRAD, U_L1, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
     default: break;
     }
     if constexpr (CONV) {   // tol = 0 keeps the blocked kernels for these two
-        if (updater == U_SIMPLE) return split_dispatch_nv<S, T, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant);
-        if (updater == U_SQUARED_L2) return split_dispatch_nv<S, T, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant);
+        if (updater == U_SIMPLE) return split_dispatch_nv<S, T, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant, ring);
+        if (updater == U_SQUARED_L2) return split_dispatch_nv<S, T, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant, ring);
     }
     return -3;
 }
 
 template <typename S, typename T, int GRAD>
 int split_dispatch_upd(const ChainLaunch& L, const KParams& kp, int updater, int64_t min_ld, int64_t max_ld,
-                       size_t lds, hipStream_t st, int* variant) {
+                       size_t lds, hipStream_t st, int* variant, int* ring) {
     // the per-sample convergence test runs exactly when tol > 0 (psgd_capi.cpp: check_conv)
-    if (kp.tol > 0.0) return split_dispatch_conv<S, T, GRAD, true>(L, kp, updater, min_ld, max_ld, lds, st, variant);
-    return split_dispatch_conv<S, T, GRAD, false>(L, kp, updater, min_ld, max_ld, lds, st, variant);
+    if (kp.tol > 0.0) return split_dispatch_conv<S, T, GRAD, true>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
+    return split_dispatch_conv<S, T, GRAD, false>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
 }
 
 template <typename S, typename T>
 int split_dispatch_grad(const ChainLaunch& L, const KParams& kp, int gradient, int updater, int64_t min_ld,
-                        int64_t max_ld, size_t lds, hipStream_t st, int* variant) {
+                        int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
     switch (gradient) {
-    case G_LOGISTIC: return split_dispatch_upd<S, T, G_LOGISTIC>(L, kp, updater, min_ld, max_ld, lds, st, variant);
-    case G_LEAST_SQUARES: return split_dispatch_upd<S, T, G_LEAST_SQUARES>(L, kp, updater, min_ld, max_ld, lds, st, variant);
-    case G_HINGE: return split_dispatch_upd<S, T, G_HINGE>(L, kp, updater, min_ld, max_ld, lds, st, variant);
+    case G_LOGISTIC: return split_dispatch_upd<S, T, G_LOGISTIC>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
+    case G_LEAST_SQUARES: return split_dispatch_upd<S, T, G_LEAST_SQUARES>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
+    case G_HINGE: return split_dispatch_upd<S, T, G_HINGE>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
     default: return -3;
     }
 }
@@ -770,15 +776,15 @@ bool split_path_applies(int layout, int updater, bool check_conv, int storage, i
 
 int launch_split_chains(const ChainLaunch& L, const KParams& kp, int storage, int compute, int gradient,
                         int updater, int64_t min_ld, int64_t max_ld, int lds_spread, hipStream_t st,
-                        int* variant) {
+                        int* variant, int* ring) {
     if (!split_path_applies(kDense, updater, kp.tol > 0.0, storage, max_ld)) return -3;
     const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
     if (storage == 1) {
-        if (compute == 1) return split_dispatch_grad<float, float>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant);
-        return split_dispatch_grad<float, double>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant);
+        if (compute == 1) return split_dispatch_grad<float, float>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
+        return split_dispatch_grad<float, double>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
     }
-    if (compute == 1) return split_dispatch_grad<double, float>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant);
-    return split_dispatch_grad<double, double>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant);
+    if (compute == 1) return split_dispatch_grad<double, float>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
+    return split_dispatch_grad<double, double>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
 }
 
 #endif  // PSGD_NO_DISPATCH
