@@ -123,43 +123,6 @@ __device__ __forceinline__ double dpp_shr_d(double v, int sh) {
     return sh == 1 ? dpp_mov<0x111>(v) : sh == 2 ? dpp_mov<0x112>(v) : dpp_mov<0x114>(v);
 }
 
-// c = -s * mult(z, y) for the gradient (vector form; only lane row_lane(i) matters at step i).
-//   Logistic: mult = 1/(1+exp(-z)) - y;  LeastSquares: mult = z - y;  Hinge: mult = 1 > ls*z ? -ls : 0
-template <int GRAD>
-__device__ __forceinline__ float coef(float z, float y, float s, float ns, float aux) {
-    if constexpr (GRAD == G_LEAST_SQUARES) {
-        return __builtin_fmaf(ns, z, aux);            // aux = s*y: -s*z + s*y
-    } else if constexpr (GRAD == G_LOGISTIC) {
-        // z is u = -log2(e) * dot: 1/(1+exp(-dot)) = 1/(1+2^u); aux = s*y
-        const float sig = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z));
-        return __builtin_fmaf(ns, sig, aux);
-    } else {
-        return (aux * z < 1.0f) ? s * aux : 0.0f;     // aux = ls = 2y - 1: -s * (-ls)
-    }
-}
-
-// MLUtils.log1pExp with the hardware exp2/log2 (fp32 throughput mode: ~1e-7 absolute)
-__device__ __forceinline__ float fast_log1p_exp(float x) {
-    const float ax = __builtin_fabsf(x);
-    const float l = __logf(1.0f + __expf(-ax));
-    return x > 0.0f ? x + l : l;
-}
-
-template <int GRAD>
-__device__ __forceinline__ float row_loss(float z, float y, float aux) {
-    if constexpr (GRAD == G_LEAST_SQUARES) {
-        const float m = z - y;
-        return m * m;                                  // halved once at the end (exact)
-    } else if constexpr (GRAD == G_LOGISTIC) {
-        const float margin = -z;
-        const float l = fast_log1p_exp(margin);
-        return y > 0.0f ? l : l - margin;
-    } else {
-        const float lz = aux * z;
-        return (1.0f > lz) ? 1.0f - lz : 0.0f;
-    }
-}
-
 // floats per Gram ring slot: the 8x8 triangle, and with the per-sample break the 8 row norms
 template <bool CONV>
 constexpr int gram_slot32() { return kBlk * kBlk + (CONV ? kBlk : 0); }

@@ -122,31 +122,6 @@ __host__ __device__ constexpr int row_lane64(int i) {
 }
 
 
-#ifndef PSGD_B64_FAST_SIGMOID
-#define PSGD_B64_FAST_SIGMOID 1
-#endif
-
-// c = (-s) * mult(z, y): the step the row's gradient takes ([ext] MLlib 1.6.1 Gradient.compute,
-// SGDUpdater.scala:95 / :178 axpy(-thisIterStepSize, gradient, w)).
-//   Logistic: mult = 1/(1 + exp(-z)) - y;  LeastSquares: mult = z - y;
-//   Hinge: mult = 1 > ls*z ? -ls : 0 (ls = 2y - 1; the empty gradient adds nothing)
-template <int GRAD>
-__device__ __forceinline__ double coef64(double z, double y, double ns) {
-    if constexpr (GRAD == G_LEAST_SQUARES) {
-        return ns * (z - y);
-    } else if constexpr (GRAD == G_LOGISTIC) {
-        const double margin = -z;
-#if PSGD_B64_FAST_SIGMOID
-        return ns * (recip_one_plus_exp(margin) - y);
-#else
-        return ns * ((1.0 / (1.0 + exp(margin))) - y);
-#endif
-    } else {
-        const double ls = 2.0 * y - 1.0;
-        return (1.0 > ls * z) ? ns * (-ls) : 0.0;
-    }
-}
-
 // The row's loss ([ext] MLlib 1.6.1): LeastSquares diff*diff/2.0; Hinge 1 - ls*z or 0.
 // (Logistic's loss is evaluated after the chain from the stored z, logistic_loss64_kernel.)
 template <int GRAD>

@@ -238,9 +238,10 @@ __device__ __forceinline__ double one_minus_pow_iter(double r, double iter) {
 // (truncation < 1e-14 relative; degree 13 until round 4, two more FMAs on every row's critical
 // path for digits the 1e-9 bar does not use) evaluated Estrin-style (depth 4), 2^k by ldexp;
 // the reciprocal by v_rcp_f64 and one Newton step (above). Within ~1e-14 relative of the
-// reference's 1.0 / (1.0 + exp(margin)) (the fp64 mode's bar is 1e-9 relative). m is clamped to
-// [-746, 709] (exp(-746) is 0 in f64; beyond 709 the result is ~1e-308 instead of 0); a NaN
-// stays NaN.
+// reference's 1.0 / (1.0 + exp(margin)) while that is a normal double (the fp64 mode's bar is 1e-9
+// relative; for m > 708.4 the result is a denormal, kept, within a few multiples of 2^-1074). m is
+// clamped to [-746, 709] (exp(-746) is 0 in f64; beyond 709 the result is ~1e-308 instead of 0);
+// a NaN stays NaN.
 __device__ __forceinline__ double recip_one_plus_exp(double m) {
     m = m > 709.0 ? 709.0 : m;
     m = m < -746.0 ? -746.0 : m;
@@ -287,8 +288,14 @@ __device__ __forceinline__ T gradient_scalar(T z, T y, T& mult) {
     if constexpr (GRAD == G_LOGISTIC) {
         T margin = -z;                                    // -1.0 * dot(data, weights)
         mult = (T(1) / (T(1) + m_exp(margin))) - y;
-        T l = log1p_exp(margin);
-        return y > T(0) ? l : l - margin;
+        if constexpr (sizeof(T) == 4) {
+            // fp32: log1pExp(m) - m = log1pExp(-m) without the cancellation (softplus_fast's
+            // comment); the f64 form below is the reference's, operation for operation
+            return log1p_exp(y > T(0) ? margin : -margin);
+        } else {
+            T l = log1p_exp(margin);
+            return y > T(0) ? l : l - margin;
+        }
     } else if constexpr (GRAD == G_LEAST_SQUARES) {
         T diff = z - y;
         mult = diff;
@@ -300,6 +307,34 @@ __device__ __forceinline__ T gradient_scalar(T z, T y, T& mult) {
         mult = on ? -ls : T(0);
         return on ? T(1) - lz : T(0);
     }
+}
+
+// log(1 + exp(t)) in fp32 with the hardware exp2 / log2, accurate RELATIVE to the result: the
+// Logistic row loss of the fp32 kernels is softplus_fast(margin) for label 1 and
+// softplus_fast(-margin) for label 0 (log1pExp(m) - m = log1pExp(-m)), so a well-classified row's
+// small loss is computed directly and never as the difference of two numbers near |margin|.
+// (Until this form the loss was __logf(1 + __expf(-|m|)) [+ m] [- m]: exactly 0 once
+// exp(-|m|) < 2^-24, and rounded to ulp(|m|) for label 0.)
+//   e = exp(-|t|) <= 1;  log1p(e) = e - e^2/2 + ... - e^6/6 for e < 1/16 (next term e^7/7:
+//   2^-26 relative), __logf(1 + e) above (result >= 0.0606);  + t for t > 0.
+// Error, relative to the result L, for t <= 0: e's relative error is |t| 2^-24 from rounding the
+// product t * log2(e) (ln2 * log2(e) = 1), half that from the constant, 2 ulp for v_exp_f32:
+// <= 2^-24 (1.5 |t| + 4); d log L / d log e <= 1, so L inherits at most that. The series adds
+// ~2 ulp of roundings (2^-22); the log branch 2^-24 absolute (rounding 1 + e) on L >= 0.0606 and
+// 1 ulp each for v_log_f32 and the product with ln2: <= 2^-24 (16.5 + 4). Together
+//   |softplus_fast(t) - L| <= 2^-24 (1.5 |t| + 24) L   while e is a normal float (|t| < 87),
+// and for t > 0 the sum t + log1p(e) adds half an ulp to the same bound. In absolute terms that
+// is within 1e-7 max(1, L) of L up to roundings of |t| (tests/test_gpu_math_edges.py holds the
+// functions to both). t = -inf gives 0, +inf gives inf, NaN stays NaN.
+__device__ __forceinline__ float softplus_fast(float t) {
+    const float e = __expf(-__builtin_fabsf(t));
+    float p = __builtin_fmaf(e, -1.0f / 6, 1.0f / 5);
+    p = __builtin_fmaf(e, p, -1.0f / 4);
+    p = __builtin_fmaf(e, p, 1.0f / 3);
+    p = __builtin_fmaf(e, p, -0.5f);
+    p = __builtin_fmaf(e, p, 1.0f);
+    const float l = e < 0.0625f ? e * p : __logf(1.0f + e);
+    return t > 0.0f ? t + l : l;
 }
 
 // fp32 CSR chains (psgd_sparse*.hip): the sample's update coefficient c = -s * mult (the row's
@@ -314,9 +349,7 @@ __device__ __forceinline__ float sparse_coef(float z, float y, float s, float& l
         const float margin = -z;
         const float e = __expf(margin);
         const float sig = __builtin_amdgcn_rcpf(1.0f + e);
-        const float ax = __builtin_fabsf(margin);
-        const float l = __logf(1.0f + __expf(-ax)) + (margin > 0.0f ? margin : 0.0f);
-        loss = y > 0.0f ? l : l - margin;
+        loss = softplus_fast(y > 0.0f ? margin : -margin);
         return -s * (sig - y);
     } else {
         const float ls = 2.0f * y - 1.0f;
@@ -324,6 +357,67 @@ __device__ __forceinline__ float sparse_coef(float z, float y, float s, float& l
         const bool on = 1.0f > lz;
         loss = on ? 1.0f - lz : 0.0f;
         return on ? s * ls : 0.0f;
+    }
+}
+
+// chain_block (fp32): c = -s * mult(z, y) for the gradient (vector form; only lane row_lane(i)
+// matters at step i).
+//   Logistic: mult = 1/(1+exp(-z)) - y;  LeastSquares: mult = z - y;  Hinge: mult = 1 > ls*z ? -ls : 0
+template <int GRAD>
+__device__ __forceinline__ float coef(float z, float y, float s, float ns, float aux) {
+    if constexpr (GRAD == G_LEAST_SQUARES) {
+        return __builtin_fmaf(ns, z, aux);            // aux = s*y: -s*z + s*y
+    } else if constexpr (GRAD == G_LOGISTIC) {
+        // z is u = -log2(e) * dot: 1/(1+exp(-dot)) = 1/(1+2^u); aux = s*y
+        const float sig = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z));
+        return __builtin_fmaf(ns, sig, aux);
+    } else {
+        return (aux * z < 1.0f) ? s * aux : 0.0f;     // aux = ls = 2y - 1: -s * (-ls)
+    }
+}
+
+
+// chain_block (fp32): the row's loss (Logistic runs take it from margin_loss_kernel instead).
+template <int GRAD>
+__device__ __forceinline__ float row_loss(float z, float y, float aux) {
+    if constexpr (GRAD == G_LEAST_SQUARES) {
+        const float m = z - y;
+        return m * m;                                  // halved once at the end (exact)
+    } else if constexpr (GRAD == G_LOGISTIC) {
+        return softplus_fast(y > 0.0f ? -z : z);       // margin = -z
+    } else {
+        const float lz = aux * z;
+        return (1.0f > lz) ? 1.0f - lz : 0.0f;
+    }
+}
+
+// chain_split (fp32 compute), Logistic: mult = 1/(1 + exp(-z)) - y with the hardware exp2 / rcp.
+__device__ __forceinline__ float sigmoid_mult_fast(float z, float y) {
+    return __builtin_amdgcn_rcpf(1.0f + __expf(-z)) - y;
+}
+
+#ifndef PSGD_B64_FAST_SIGMOID
+#define PSGD_B64_FAST_SIGMOID 1
+#endif
+
+// chain_block64: c = (-s) * mult(z, y): the step the row's gradient takes ([ext] MLlib 1.6.1
+// Gradient.compute, SGDUpdater.scala:95 / :178 axpy(-thisIterStepSize, gradient, w)).
+//   Logistic: mult = 1/(1 + exp(-z)) - y;  LeastSquares: mult = z - y;
+//   Hinge: mult = 1 > ls*z ? -ls : 0 (ls = 2y - 1; the empty gradient adds nothing)
+template <int GRAD>
+__device__ __forceinline__ double coef64(double z, double y, double ns) {
+    if constexpr (GRAD == G_LEAST_SQUARES) {
+        return ns * (z - y);
+    } else if constexpr (GRAD == G_LOGISTIC) {
+        const double margin = -z;
+#if PSGD_B64_FAST_SIGMOID
+        return ns * (recip_one_plus_exp(margin) - y);
+#else
+        return ns * ((1.0 / (1.0 + exp(margin))) - y);
+#endif
+    } else {
+        const double ls = 2.0 * y - 1.0;
+        return (1.0 > ls * z) ? ns * (-ls) : 0.0;
     }
 }
 

@@ -441,7 +441,7 @@ __global__ __launch_bounds__(64 * (H + 1)) void chain_split(ChainLaunch L, KPara
         if constexpr (ZOUT) {
             // 1/(1 + exp(margin)) - y, margin = -z; the row's loss from z after the chain
             if constexpr (sizeof(T) == 8) mult = recip_one_plus_exp(-z) - y;
-            else mult = __builtin_amdgcn_rcpf(1.0f + __expf(-z)) - y;
+            else mult = sigmoid_mult_fast(z, y);
             zprev = z;
         } else {
             T loss;
