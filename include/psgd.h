@@ -302,6 +302,58 @@ int32_t psgd_gd_update_device(psgd_ctx* ctx, int32_t updater, int32_t d, const d
                               double step_size, int32_t iteration, double reg_param, double* d_w_out,
                               double* d_regval_out, void* stream);
 
+/* Binary classification metrics (MLlib 1.6.1 BinaryClassificationMetrics with numBins = 0, as this
+ * project states it: DESIGN.md §3 has the definitions) of n (score, label) pairs of doubles. A pair
+ * is positive when label > 0.5. Scores are keys in java.lang.Double.compare order (-0.0 < 0.0 are
+ * two keys; +-Inf and denormals are ordinary keys; NaN is outside the contract). The groups are the
+ * distinct scores in descending order, g = 0 .. G - 1:
+ *   thresholds[g]  the group's score, bit for bit;
+ *   cum_pos[g], cum_neg[g]  the positives / negatives with score >= thresholds[g].
+ * The three arrays hold n entries each (G <= n are written) and may be NULL as a set when only the
+ * areas are wanted. summary[4] = {G, P, N, rocNumerator}, P = cum_pos[G - 1], N = cum_neg[G - 1],
+ *   rocNumerator = sum_g (cum_neg[g] - cum_neg[g - 1]) (cum_pos[g] + cum_pos[g - 1]), cum[-1] = 0,
+ * exact in 64 bits. areas[2] = {areaUnderROC, areaUnderPR}:
+ *   areaUnderROC = (double)rocNumerator / (2.0 P N): the trapezoid area of (0, 0), (cum_neg / N,
+ *                  cum_pos / P).., (1, 1) in exact integers, divided once; 0.0 when P = 0, 1.0 when
+ *                  N = 0 (P > 0), NaN when n = 0;
+ *   areaUnderPR    the trapezoid area of (0.0, 1.0), (cum_pos / P, cum_pos / (cum_pos + cum_neg))..
+ *                  (recall 0.0 when P = 0), summed in fp64: fixed-size tiles of groups summed in a
+ *                  fixed order, the tiles added in tile order -- the same bits from call to call.
+ * Nothing uses floating-point atomics; the table and the integers do not depend on the input order.
+ * n = 0 launches no kernel: summary is zeros, areas {NaN, 0.0}. n >= 2^31 is PSGD_EUNSUPPORTED.
+ * Errors: PSGD_EINVAL for a null ctx, n < 0, null scores / labels (n > 0), null summary / areas, or
+ * a table of which only some arrays are NULL. No partition need be registered.
+ * The host-pointer form runs on the context's stream and returns when the outputs are written. The
+ * _device form takes device pointers and a stream (NULL: the context's) and is enqueued without a
+ * host synchronisation. Scratch (two pair buffers and the tile tables) is the context's own; ordering
+ * as for the scoring calls. */
+int32_t psgd_binary_counts(psgd_ctx* ctx, const double* scores, const double* labels, int64_t n,
+                           double* thresholds, int64_t* cum_pos, int64_t* cum_neg, int64_t* summary,
+                           double* areas);
+int32_t psgd_binary_counts_device(psgd_ctx* ctx, const double* d_scores, const double* d_labels, int64_t n,
+                                  double* d_thresholds, int64_t* d_cum_pos, int64_t* d_cum_neg,
+                                  int64_t* d_summary, double* d_areas, void* stream);
+
+/* The same outputs for every registered row at weights w (d long): the score is the row's raw
+ * margin x_r . w from the psgd_predict kernels, written into scratch in partition-index order; the
+ * labels are the ones the registry holds on the device (nothing is copied). The table arrays hold
+ * one entry per registered row. Errors: PSGD_EINVAL for a null ctx / w / summary / areas or a
+ * partial table, PSGD_ESTATE when no partition is registered, PSGD_EUNSUPPORTED for 2^31 rows or
+ * more; a registry of empty partitions is n = 0. Like psgd_evaluate the calls wait for registration
+ * copies in flight, order themselves against an epoch running on another stream and leave the
+ * epoch state alone (psgd_ctx_last_kernel, psgd_ctx_chain_launches and the chain times are
+ * unchanged; a sampled epoch's batch plays no part). */
+int32_t psgd_binary_counts_model(psgd_ctx* ctx, const double* w, double* thresholds, int64_t* cum_pos,
+                                 int64_t* cum_neg, int64_t* summary, double* areas);
+int32_t psgd_binary_counts_model_device(psgd_ctx* ctx, const double* d_w, double* d_thresholds,
+                                        int64_t* d_cum_pos, int64_t* d_cum_neg, int64_t* d_summary,
+                                        double* d_areas, void* stream);
+
+/* The number of pairs one workgroup of the metrics kernels sorts, scans or sums (a tile): the sizes
+ * at which those kernels change path are its multiples, and 256 tiles are one sweep of the sort's
+ * table scan. */
+int32_t psgd_metrics_sort_tile(void);
+
 /* Diagnostics: which chain kernel the last epoch launched (DESIGN.md §3 has the table):
  * 100 + NV   per-sample dense chain (chain_dense), NV 16-byte row vectors per lane;
  * 200 / 201  general dense / CSR chain (chain_general);

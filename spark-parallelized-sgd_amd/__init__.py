@@ -19,10 +19,12 @@ from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine,
 from .gradient_descent import GradientDescent, GradientSum, gradient_sum, runMiniBatchSGD
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
+from .evaluation import BinaryClassificationMetrics
 from .util import loadLibSVMFile
 
 __all__ = [
     "ParallelizedSGD", "runParallelizedSGD", "evaluate", "Evaluation", "HipEngine",
+    "BinaryClassificationMetrics",
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",

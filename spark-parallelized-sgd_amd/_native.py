@@ -31,6 +31,8 @@ EXPORTED = (
     "psgd_evaluate", "psgd_evaluate_device", "psgd_predict", "psgd_predict_device",
     "psgd_column_stats", "psgd_column_stats_device", "psgd_transform_columns", "psgd_transform_columns_device",
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
+    "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
+    "psgd_metrics_sort_tile",
 )
 
 
@@ -135,6 +137,11 @@ def lib():
                                C.c_int32),
             "psgd_gd_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp,
                                        vp], C.c_int32),
+            "psgd_binary_counts": ([vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_binary_counts_device": ([vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_binary_counts_model": ([vp, vp, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_binary_counts_model_device": ([vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_metrics_sort_tile": ([], C.c_int32),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -178,6 +185,11 @@ def sample_partition(seed: int, n: int, fraction: float, device: int = 0):
     check(lib().psgd_sample_partition(device, int(seed), int(n), float(fraction), rows.ctypes.data,
                                       C.byref(m)))
     return rows[: m.value].copy()
+
+
+def metrics_sort_tile() -> int:
+    """The pairs one workgroup of the metrics kernels takes (psgd_metrics_sort_tile)."""
+    return int(lib().psgd_metrics_sort_tile())
 
 
 class _PinnedBuffer:
@@ -429,3 +441,35 @@ class Context:
                          stream=None):
         check(self._L.psgd_gd_update_device(self.handle, int(updater), int(d), w_ptr, sum_ptr, float(step),
                                             int(iteration), float(reg), w_out_ptr, regval_ptr, stream))
+
+    # binary classification metrics ------------------------------------------------------------------
+    def binary_counts(self, scores, labels, table: bool = True):
+        """Host-pointer form (psgd_binary_counts): (thresholds, cumPos, cumNeg, summary, areas) of host
+        scores and labels; the three table arrays hold G rows, or are None with table=False.
+        summary = [G, P, N, rocNumerator], areas = [areaUnderROC, areaUnderPR]."""
+        import numpy as np
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        labels = np.ascontiguousarray(labels, dtype=np.float64)
+        n = int(scores.shape[0])
+        summary, areas = np.zeros(4, dtype=np.int64), np.zeros(2, dtype=np.float64)
+        thr = np.zeros(max(n, 1), dtype=np.float64) if table else None
+        cp = np.zeros(max(n, 1), dtype=np.int64) if table else None
+        cn = np.zeros(max(n, 1), dtype=np.int64) if table else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        check(self._L.psgd_binary_counts(self.handle, scores.ctypes.data, labels.ctypes.data, n, ptr(thr), ptr(cp),
+                                         ptr(cn), summary.ctypes.data, areas.ctypes.data))
+        G = int(summary[0])
+        if not table:
+            return None, None, None, summary, areas
+        return thr[:G].copy(), cp[:G].copy(), cn[:G].copy(), summary, areas
+
+    def binary_counts_device(self, scores_ptr, labels_ptr, n, thr_ptr, cp_ptr, cn_ptr, summary_ptr, areas_ptr,
+                             stream=None):
+        """psgd_binary_counts_device: enqueued on `stream`; every pointer on the device."""
+        check(self._L.psgd_binary_counts_device(self.handle, scores_ptr, labels_ptr, C.c_int64(n), thr_ptr, cp_ptr,
+                                                cn_ptr, summary_ptr, areas_ptr, stream))
+
+    def binary_counts_model_device(self, w_ptr, thr_ptr, cp_ptr, cn_ptr, summary_ptr, areas_ptr, stream=None):
+        """psgd_binary_counts_model_device: every registered row scored at w; enqueued on `stream`."""
+        check(self._L.psgd_binary_counts_model_device(self.handle, w_ptr, thr_ptr, cp_ptr, cn_ptr, summary_ptr,
+                                                      areas_ptr, stream))

@@ -458,6 +458,9 @@ struct psgd_ctx {
     // the tile records with the two-pass path's multipliers and the update's block sums, and the
     // host-pointer forms' staging
     DevBuf gdescs, grows, gys, gxstate, grec, gio;
+    // binary classification metrics (psgd_binary_counts*): the sort's pair buffers and tile tables
+    // (with a table of the call's own and the model forms' margins), and the host-pointer forms' staging
+    DevBuf mscratch, mio;
 };
 
 namespace {
@@ -821,6 +824,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->eparts, &ctx->etiles, &ctx->epart, &ctx->ew, &ctx->emargins,
                           &ctx->stile0, &ctx->srec, &ctx->sio,
                           &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
+                          &ctx->mscratch, &ctx->mio,
                           &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
@@ -1707,6 +1711,227 @@ int32_t psgd_predict(psgd_ctx* ctx, int64_t part, const double* w, double* margi
     HIP_TRY(hipMemcpyAsync(margins, d_m, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PSGD_OK;
+}
+
+// ---- Binary classification metrics (kernels in psgd_metrics.hip) ----
+// The same place in the context as the scoring calls: scratch of their own (ctx->mscratch, and
+// ctx->mio for the host-pointer forms' staging), no epoch state touched. The array forms read no
+// partition; the model forms score every partition with the predict kernels first (score_prepare).
+
+int32_t psgd_metrics_sort_tile(void) { return psgd::metrics_tile(); }
+
+static int32_t metrics_args(int64_t n, const void* scores, const void* labels, const void* thresholds,
+                            const void* cum_pos, const void* cum_neg, const void* summary, const void* areas) {
+    if (n < 0) return fail(PSGD_EINVAL, "n must be >= 0");
+    if (n > (int64_t)INT32_MAX)
+        return fail(PSGD_EUNSUPPORTED, "binary classification metrics over 2^31 pairs or more");
+    if (n > 0 && (!scores || !labels)) return fail(PSGD_EINVAL, "scores/labels are null");
+    if (!summary || !areas) return fail(PSGD_EINVAL, "summary/areas are null");
+    const int given = (thresholds ? 1 : 0) + (cum_pos ? 1 : 0) + (cum_neg ? 1 : 0);
+    if (given != 0 && given != 3)
+        return fail(PSGD_EINVAL, "thresholds, cum_pos and cum_neg are given together or not at all");
+    return PSGD_OK;
+}
+
+// No pairs: summary zeros, areas {NaN (0 / 0), 0.0}, without a kernel.
+static int32_t metrics_empty(int64_t* d_summary, double* d_areas, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(d_summary, 0, 4 * sizeof(int64_t), st));
+    HIP_TRY(hipMemsetAsync(d_areas, 0, 2 * sizeof(double), st));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)(reinterpret_cast<char*>(d_areas) + 4), 0x7FF80000, 1, st));
+    return PSGD_OK;
+}
+
+// The scratch of a call over n pairs carved from ctx->mscratch (ctx->mu held): the kernels' buffers,
+// a table of the call's own when the caller wants none (*cum_pos / *cum_neg), and the model forms'
+// margins.
+static int32_t metrics_scratch(psgd_ctx* ctx, int64_t n, bool own_table, bool want_margins, psgd::MetricsBufs* B,
+                               int64_t** cum_pos, int64_t** cum_neg, double** margins) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t N = (size_t)n, nt = (N + (size_t)psgd::metrics_tile() - 1) / (size_t)psgd::metrics_tile();
+    const size_t keys = up(N * 8), bytes = up(N), table = up(256 * nt * 4), ghist = up(8 * 256 * 4), plan = 256,
+                 tile = up(nt * 8);
+    const size_t total = 2 * keys + 2 * bytes + table + ghist + plan + 3 * tile + (own_table ? 2 * keys : 0) +
+                         (want_margins ? keys : 0);
+    HIP_TRY(ctx->mscratch.ensure(total));
+    char* p = ctx->mscratch.as<char>();
+    auto take = [&p](size_t b) {
+        char* q = p;
+        p += b;
+        return q;
+    };
+    B->keys[0] = reinterpret_cast<uint64_t*>(take(keys));
+    B->keys[1] = reinterpret_cast<uint64_t*>(take(keys));
+    B->bytes[0] = reinterpret_cast<uint8_t*>(take(bytes));
+    B->bytes[1] = reinterpret_cast<uint8_t*>(take(bytes));
+    B->table = reinterpret_cast<unsigned*>(take(table));
+    B->ghist = reinterpret_cast<unsigned*>(take(ghist));
+    B->plan = reinterpret_cast<int*>(take(plan));
+    B->tile_heads = reinterpret_cast<int64_t*>(take(tile));
+    B->tile_pos = reinterpret_cast<int64_t*>(take(tile));
+    B->tile_pr = reinterpret_cast<double*>(take(tile));
+    if (own_table) {
+        *cum_pos = reinterpret_cast<int64_t*>(take(keys));
+        *cum_neg = reinterpret_cast<int64_t*>(take(keys));
+    }
+    if (want_margins) *margins = reinterpret_cast<double*>(take(keys));
+    return PSGD_OK;
+}
+
+static int32_t metrics_launch_failed(int e) {
+    return fail(PSGD_EDEVICE, std::string("metrics kernel launch failed: ") + hipGetErrorString((hipError_t)e));
+}
+
+int32_t psgd_binary_counts_device(psgd_ctx* ctx, const double* d_scores, const double* d_labels, int64_t n,
+                                  double* d_thresholds, int64_t* d_cum_pos, int64_t* d_cum_neg,
+                                  int64_t* d_summary, double* d_areas, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = metrics_args(n, d_scores, d_labels, d_thresholds, d_cum_pos, d_cum_neg, d_summary, d_areas);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = scratch_acquire(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    if (n == 0) return metrics_empty(d_summary, d_areas, st);
+    psgd::MetricsBufs B;
+    rc = metrics_scratch(ctx, n, !d_cum_pos, false, &B, &d_cum_pos, &d_cum_neg, nullptr);
+    if (rc) return rc;
+    int e = psgd::launch_metrics_begin(B, st);
+    if (!e) e = psgd::launch_metrics_keys(B, d_scores, d_labels, 0, n, ctx->num_cus, st);
+    if (!e) e = psgd::launch_metrics_finish(B, n, d_thresholds, d_cum_pos, d_cum_neg, d_summary, d_areas, st);
+    return e ? metrics_launch_failed(e) : PSGD_OK;
+}
+
+int32_t psgd_binary_counts_model_device(psgd_ctx* ctx, const double* d_w, double* d_thresholds,
+                                        int64_t* d_cum_pos, int64_t* d_cum_neg, int64_t* d_summary,
+                                        double* d_areas, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_w) return fail(PSGD_EINVAL, "d_w is null");
+    int32_t rc = metrics_args(0, nullptr, nullptr, d_thresholds, d_cum_pos, d_cum_neg, d_summary, d_areas);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    int64_t n = 0;
+    for (auto& kv : ctx->parts) n += kv.second.n_rows;
+    if (n > (int64_t)INT32_MAX)
+        return fail(PSGD_EUNSUPPORTED, "binary classification metrics over 2^31 rows or more");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    if (n == 0) return metrics_empty(d_summary, d_areas, st);
+    psgd::MetricsBufs B;
+    double* margins = nullptr;
+    rc = metrics_scratch(ctx, n, !d_cum_pos, true, &B, &d_cum_pos, &d_cum_neg, &margins);
+    if (rc) return rc;
+    int e = psgd::launch_metrics_begin(B, st);
+    if (e) return metrics_launch_failed(e);
+    int64_t off = 0;
+    size_t p = 0;
+    for (auto& kv : ctx->parts) {
+        const Part& q = kv.second;
+        if (q.n_rows > 0) {
+            // (the dot needs no loss: LeastSquares' is the cheapest to throw away)
+            rc = score_enqueue(ctx, PSGD_GRADIENT_LEAST_SQUARES, p, 1, d_w, nullptr, nullptr, margins + off, st);
+            if (rc) return rc;
+            e = psgd::launch_metrics_keys(B, margins + off, q.y, off, q.n_rows, ctx->num_cus, st);
+            if (e) return metrics_launch_failed(e);
+            off += q.n_rows;
+        }
+        ++p;
+    }
+    e = psgd::launch_metrics_finish(B, n, d_thresholds, d_cum_pos, d_cum_neg, d_summary, d_areas, st);
+    return e ? metrics_launch_failed(e) : PSGD_OK;
+}
+
+// The host-pointer forms' way back: {summary[4], areas[2]} at d_out, then the first G rows of the
+// table staged at d_table (three arrays of `stride` entries).
+static int32_t metrics_read_back(psgd_ctx* ctx, const char* d_out, const char* d_table, size_t stride,
+                                 double* thresholds, int64_t* cum_pos, int64_t* cum_neg, int64_t* summary,
+                                 double* areas) {
+    DeviceGuard g(ctx->device);
+    char h[48];
+    HIP_TRY(hipMemcpyAsync(h, d_out, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(summary, h, 32);
+    std::memcpy(areas, h + 32, 16);
+    const size_t G = (size_t)summary[0];
+    if (!thresholds || G == 0) return PSGD_OK;
+    HIP_TRY(hipMemcpyAsync(thresholds, d_table, G * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(cum_pos, d_table + stride * 8, G * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(cum_neg, d_table + 2 * stride * 8, G * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_binary_counts(psgd_ctx* ctx, const double* scores, const double* labels, int64_t n,
+                           double* thresholds, int64_t* cum_pos, int64_t* cum_neg, int64_t* summary,
+                           double* areas) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = metrics_args(n, scores, labels, thresholds, cum_pos, cum_neg, summary, areas);
+    if (rc) return rc;
+    const size_t N = (size_t)n;
+    char* base = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        // {summary[4], areas[2], scores[n], labels[n], thresholds[n], cum_pos[n], cum_neg[n]}
+        HIP_TRY(ctx->mio.ensure(48 + (thresholds ? 5 : 2) * N * 8 + 8));
+        base = ctx->mio.as<char>();
+        if (N) {
+            HIP_TRY(hipMemcpyAsync(base + 48, scores, N * 8, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(base + 48 + N * 8, labels, N * 8, hipMemcpyHostToDevice, ctx->stream));
+            // the caller's arrays are pageable in general: the copies have left them when this returns
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    char* d_table = base + 48 + 2 * N * 8;
+    rc = psgd_binary_counts_device(ctx, reinterpret_cast<double*>(base + 48),
+                                   reinterpret_cast<double*>(base + 48 + N * 8), n,
+                                   thresholds ? reinterpret_cast<double*>(d_table) : nullptr,
+                                   thresholds ? reinterpret_cast<int64_t*>(d_table + N * 8) : nullptr,
+                                   thresholds ? reinterpret_cast<int64_t*>(d_table + 2 * N * 8) : nullptr,
+                                   reinterpret_cast<int64_t*>(base), reinterpret_cast<double*>(base + 32), ctx->stream);
+    if (rc) return rc;
+    return metrics_read_back(ctx, base, d_table, N, thresholds, cum_pos, cum_neg, summary, areas);
+}
+
+int32_t psgd_binary_counts_model(psgd_ctx* ctx, const double* w, double* thresholds, int64_t* cum_pos,
+                                 int64_t* cum_neg, int64_t* summary, double* areas) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!w) return fail(PSGD_EINVAL, "w is null");
+    int32_t rc = metrics_args(0, nullptr, nullptr, thresholds, cum_pos, cum_neg, summary, areas);
+    if (rc) return rc;
+    size_t N = 0, d = 0;
+    char* base = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        for (auto& kv : ctx->parts) N += (size_t)kv.second.n_rows;
+        d = (size_t)ctx->parts.begin()->second.d;
+        DeviceGuard g(ctx->device);
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        // {summary[4], areas[2], w[d], thresholds[n], cum_pos[n], cum_neg[n]}
+        HIP_TRY(ctx->mio.ensure(48 + d * 8 + (thresholds ? 3 : 0) * N * 8 + 8));
+        base = ctx->mio.as<char>();
+        HIP_TRY(hipMemcpyAsync(base + 48, w, d * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    char* d_table = base + 48 + d * 8;
+    rc = psgd_binary_counts_model_device(ctx, reinterpret_cast<double*>(base + 48),
+                                         thresholds ? reinterpret_cast<double*>(d_table) : nullptr,
+                                         thresholds ? reinterpret_cast<int64_t*>(d_table + N * 8) : nullptr,
+                                         thresholds ? reinterpret_cast<int64_t*>(d_table + 2 * N * 8) : nullptr,
+                                         reinterpret_cast<int64_t*>(base), reinterpret_cast<double*>(base + 32),
+                                         ctx->stream);
+    if (rc) return rc;
+    return metrics_read_back(ctx, base, d_table, N, thresholds, cum_pos, cum_neg, summary, areas);
 }
 
 // ---- Column statistics and the column transform (kernels in psgd_colstats.hip) ----

@@ -263,4 +263,30 @@ int64_t gd_update_blocks(int d);
 int launch_gd_update(int updater, int d, const double* w, const double* sum, double s, double reg, double* w_out,
                      double* part, double* regval, hipStream_t st);
 
+// ---- Binary classification metrics (psgd_metrics.hip: psgd_binary_counts*) ----
+// The pairs a workgroup of the sort, the scans and the area sums takes (psgd_metrics_sort_tile).
+int32_t metrics_tile();
+// Scratch of one call over n pairs, n_tiles = ceil(n / metrics_tile()): the two (key, byte) pair
+// buffers [n] each, the digit-major tile table [256 * n_tiles], the 8 x 256 digit totals, the pass
+// plan [9], the group scan's tile sums [n_tiles] each and the PR area's tile sums [n_tiles].
+struct MetricsBufs {
+    uint64_t* keys[2];
+    uint8_t* bytes[2];
+    unsigned* table;
+    unsigned* ghist;
+    int* plan;
+    int64_t* tile_heads;
+    int64_t* tile_pos;
+    double* tile_pr;
+};
+// A call is launch_metrics_begin, launch_metrics_keys once per run of pairs (scores / labels [n]
+// become pairs offset .. offset + n of buffer 0: the model form calls it once a partition, on the
+// registry's own labels), launch_metrics_finish over all n pairs (1 <= n <= INT32_MAX): the table
+// thresholds (nullable) / cum_pos / cum_neg [n], summary[4] = {G, P, N, rocNumerator}, areas[2].
+int launch_metrics_begin(const MetricsBufs& B, hipStream_t st);
+int launch_metrics_keys(const MetricsBufs& B, const double* scores, const double* labels, int64_t offset,
+                        int64_t n, int num_cus, hipStream_t st);
+int launch_metrics_finish(const MetricsBufs& B, int64_t n, double* thresholds, int64_t* cum_pos, int64_t* cum_neg,
+                          int64_t* summary, double* areas, hipStream_t st);
+
 }  // namespace psgd

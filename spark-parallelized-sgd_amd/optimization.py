@@ -486,6 +486,86 @@ class HipEngine(ShardedEngine):
         keep.synchronize()   # w_dev may be a temporary of this call
         return out
 
+    # binary classification metrics (psgd_binary_counts_model_device / psgd_binary_counts_device) --
+    def _local_scores(self, w_dev):
+        """(margins, labels) of this rank's rows in partition order, as device tensors of doubles
+        (self.stream is current): psgd_predict_device per partition, the labels as the data holds them."""
+        torch = self.torch
+        rows = [self._data.partitions[p].n_rows for p in range(self.lo, self.hi)]
+        scores = torch.empty(sum(rows), dtype=torch.float64, device=self.dev)
+        labels = torch.empty(sum(rows), dtype=torch.float64, device=self.dev)
+        off = 0
+        with self.ctx.engine_lock:
+            if self.n_local > 0 and self.ctx.registered_token != self._key:
+                self._register(self._data)
+            for p, n in zip(range(self.lo, self.hi), rows):
+                if n == 0:
+                    continue
+                self.ctx.predict_device(p, w_dev.data_ptr(), scores.data_ptr() + 8 * off, self.stream.cuda_stream)
+                y = self._data.partitions[p].labels
+                if not torch.is_tensor(y):
+                    y = torch.from_numpy(np.ascontiguousarray(y, dtype=np.float64))
+                labels[off: off + n].copy_(y.detach().to(device=self.dev, dtype=torch.float64))
+                off += n
+        return scores, labels
+
+    def binary_counts(self, w, score: str = "margin"):
+        """The BinaryClassificationMetrics table and areas of weights w over every partition of the
+        data, on all ranks (evaluation.DeviceCounts; include/psgd.h has the semantics). One rank with
+        score="margin": psgd_binary_counts_model_device -- the rows are scored into the context's
+        scratch and their labels read where the registry holds them. score="probability" applies
+        torch.sigmoid to the margins of psgd_predict_device and goes through the array form. With
+        several ranks each scores its own partitions, the ranks all-gather their scores and labels
+        padded to the longest (the backends of exchange()), and every rank runs the array form over
+        the whole: the result does not depend on the order of the pairs, so all ranks hold the same
+        bits, and the bits of one rank alone."""
+        from . import evaluation as E
+        if score not in ("margin", "probability"):
+            raise IllegalArgumentException(f"requirement failed: score must be 'margin' or 'probability', got {score!r}")
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            w_dev = self._score_weights(w)
+            if self.world == 1 and score == "margin" and self.n_local > 0:
+                n = sum(self._data.partitions[p].n_rows for p in range(self.lo, self.hi))
+                thr, cp, cn, small = E.alloc_outputs(torch, self.dev, n)
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    self.ctx.binary_counts_model_device(w_dev.data_ptr(), thr.data_ptr(), cp.data_ptr(), cn.data_ptr(),
+                                                        small.data_ptr(), small.data_ptr() + 32,
+                                                        self.stream.cuda_stream)
+                out = E.read_outputs(thr, cp, cn, small)
+            else:
+                scores, labels = self._local_scores(w_dev)
+                if self.world > 1:
+                    import torch.distributed as dist
+                    P = self._data.num_partitions
+                    rows = []
+                    for r in range(self.world):
+                        lo, hi = shard_range(P, r, self.world)
+                        rows.append(sum(self._data.partitions[p].n_rows for p in range(lo, hi)))
+                    width = max(max(rows), 1)
+                    buf = torch.zeros(2 * width, dtype=torch.float64, device=self.dev)
+                    buf[: rows[self.rank]].copy_(scores)
+                    buf[width: width + rows[self.rank]].copy_(labels)
+                    got = torch.empty(self.world * 2 * width, dtype=torch.float64, device=self.dev)
+                    if dist.get_backend() == "gloo":
+                        dist.all_gather(list(got.view(self.world, 2 * width).unbind(0)), buf)
+                    else:
+                        dist.all_gather_into_tensor(got, buf)
+                    got = got.view(self.world, 2, width)
+                    scores = torch.cat([got[r, 0, : rows[r]] for r in range(self.world)])
+                    labels = torch.cat([got[r, 1, : rows[r]] for r in range(self.world)])
+                if score == "probability":
+                    scores = torch.sigmoid(scores)
+                out = E.counts_of_tensors(self.ctx, torch, self.stream, scores.contiguous(), labels.contiguous())
+        # (the read of summary and areas has waited for self.stream: w_dev and the temporaries are free)
+        caller.wait_stream(self.stream)
+        for t in (out.thresholds, out.cumPos, out.cumNeg):
+            t.record_stream(caller)
+        return out
 
     # column statistics (psgd_column_stats_device) ----------------------------------------------
     def column_stats(self) -> "ColumnStats":
