@@ -354,6 +354,60 @@ int32_t psgd_binary_counts_model_device(psgd_ctx* ctx, const double* d_w, double
  * table scan. */
 int32_t psgd_metrics_sort_tile(void);
 
+/* Train/test splits on the device: RDD.randomSplit and MLUtils.kFold of Spark / MLlib 1.6.1 as
+ * this project states them (DESIGN.md §3 has the definitions). Both are BernoulliCellSampler passes:
+ * partition p with n rows draws x_0 .. x_{n-1}, x_t the t-th nextDouble() of an XORShiftRandom seeded
+ * (through hashSeed) with s_p -- always one draw a row, in iterator order, no gap sampling -- and
+ * cell(lb, ub, complement) keeps row t when lb <= x_t < ub, or with complement != 0 when
+ * x_t < lb || x_t >= ub. ub <= lb is legal: it keeps nothing, or everything with complement.
+ * The library derives s_p on the device from the registry's global partition indices:
+ *   PSGD_SEED_PLUS_INDEX     s_p = seed + p, wrapping as a Java Long (randomSplit);
+ *   PSGD_SEED_PARTITIONWISE  s_p = the p-th java.util.Random(seed).nextLong(), p from 0
+ *                            (PartitionwiseSampledRDD: kFold; the epoch sampler's seeding).
+ *
+ * psgd_cell_select: d_rows is a device int32 array with one entry per registered row; partition p's
+ * kept row indices, increasing, are written from its first row's offset on (the offsets follow the
+ * partitions in partition-index order), the entries behind them are left alone. counts[n_parts]
+ * receives the kept rows per partition and nnz[n_parts] (nullable) the sum of their CSR row lengths
+ * (zeros for dense rows), in partition-index order. The host-pointer form runs on the context's
+ * stream and returns after one synchronisation; the _device form writes both to device arrays and is
+ * enqueued on `stream` without a host synchronisation.
+ * Errors: PSGD_EINVAL for a null ctx or pointer (d_rows may be null only when no row is registered),
+ * an unknown seeding or NaN bounds; PSGD_ESTATE when no partition is registered; PSGD_EUNSUPPORTED for
+ * a partition of more than 2^31 - 1 rows, as for a sampled epoch.
+ * Integer arithmetic and comparisons only, no atomics: the same bits from call to call. Ordering and
+ * scratch as for the scoring calls; the epoch state is left alone. */
+enum psgd_seeding { PSGD_SEED_PLUS_INDEX = 0, PSGD_SEED_PARTITIONWISE = 1 };
+int32_t psgd_cell_select(psgd_ctx* ctx, int64_t seed, int32_t seeding, double lb, double ub, int32_t complement,
+                         int32_t* d_rows, int64_t* counts, int64_t* nnz);
+int32_t psgd_cell_select_device(psgd_ctx* ctx, int64_t seed, int32_t seeding, double lb, double ub,
+                                int32_t complement, int32_t* d_rows, int64_t* d_counts, int64_t* d_nnz,
+                                void* stream);
+
+/* Compaction of the registered partitions through a psgd_cell_select result into caller-allocated
+ * device buffers, every output bit for bit (no arithmetic, no atomics). d_rows is the selection's
+ * index array; counts[n_parts] (host) its counts, which the caller has read back to size the
+ * buffers. The per-partition output pointers are host arrays of device pointers in partition-index
+ * order; an entry may be null where nothing is written through it.
+ * psgd_gather_dense_device: row k of d_x_out[p] (pitch ld_out elements, ld_out >= d, 16-byte aligned
+ * rows) = registered row d_rows[offset_p + k] read at its own pitch, with columns [d, ld_out) written
+ * as zeros; d_labels_out[p][k] its label.
+ * psgd_gather_csr_device: nnz[n_parts] (host) is the selection's nnz; d_row_ptr_out[p] receives
+ * counts[p] + 1 entries starting at 0 (never null: a partition that kept nothing gets {0}), d_col_out
+ * [p] / d_val_out[p] the kept rows' nnz[p] entries back to back. A source row_ptr[0] may be non-zero.
+ * The outputs satisfy the contracts of psgd_register_dense_device / psgd_register_csr_device: they
+ * can be registered zero-copy at once. The calls only read the source (any kind of registration).
+ * Errors: PSGD_EINVAL for a null ctx or argument, a count outside [0, n_rows], a null output that is
+ * needed, a bad ld_out or rows of the other layout; PSGD_ESTATE when no partition is registered.
+ * One launch serves every partition (three for CSR). Enqueued on `stream` (NULL: the context's); the
+ * call waits once for its table of pointers to reach the device. Ordering and scratch as for the
+ * scoring calls; the epoch state is left alone. */
+int32_t psgd_gather_dense_device(psgd_ctx* ctx, const int32_t* d_rows, const int64_t* counts, int64_t ld_out,
+                                 void* const* d_x_out, double* const* d_labels_out, void* stream);
+int32_t psgd_gather_csr_device(psgd_ctx* ctx, const int32_t* d_rows, const int64_t* counts, const int64_t* nnz,
+                               double* const* d_labels_out, int64_t* const* d_row_ptr_out,
+                               int32_t* const* d_col_out, void* const* d_val_out, void* stream);
+
 /* Diagnostics: which chain kernel the last epoch launched (DESIGN.md §3 has the table):
  * 100 + NV   per-sample dense chain (chain_dense), NV 16-byte row vectors per lane;
  * 200 / 201  general dense / CSR chain (chain_general);

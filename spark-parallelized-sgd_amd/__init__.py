@@ -20,11 +20,12 @@ from .gradient_descent import GradientDescent, GradientSum, gradient_sum, runMin
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics
+from .split import kFold, randomSplit
 from .util import loadLibSVMFile
 
 __all__ = [
     "ParallelizedSGD", "runParallelizedSGD", "evaluate", "Evaluation", "HipEngine",
-    "BinaryClassificationMetrics",
+    "BinaryClassificationMetrics", "randomSplit", "kFold",
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",

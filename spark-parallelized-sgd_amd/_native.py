@@ -17,6 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 
 PSGD_OK, PSGD_EINVAL, PSGD_EUNSUPPORTED, PSGD_EDEVICE, PSGD_ENOMEM, PSGD_ESTATE = 0, -1, -2, -3, -4, -5
 F64, F32 = 0, 1
+SEED_PLUS_INDEX, SEED_PARTITIONWISE = 0, 1   # enum psgd_seeding
 
 # Symbols include/psgd.h declares (checked by tests/test_capi_symbols.py).
 EXPORTED = (
@@ -33,6 +34,7 @@ EXPORTED = (
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
+    "psgd_cell_select", "psgd_cell_select_device", "psgd_gather_dense_device", "psgd_gather_csr_device",
 )
 
 
@@ -142,6 +144,11 @@ def lib():
             "psgd_binary_counts_model": ([vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_binary_counts_model_device": ([vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_metrics_sort_tile": ([], C.c_int32),
+            "psgd_cell_select": ([vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_cell_select_device": ([vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, vp, vp, vp, vp],
+                                        C.c_int32),
+            "psgd_gather_dense_device": ([vp, vp, vp, C.c_int64, vp, vp, vp], C.c_int32),
+            "psgd_gather_csr_device": ([vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
         }
         for name, (args, res) in sig.items():
             f = getattr(L, name)
@@ -473,3 +480,47 @@ class Context:
         """psgd_binary_counts_model_device: every registered row scored at w; enqueued on `stream`."""
         check(self._L.psgd_binary_counts_model_device(self.handle, w_ptr, thr_ptr, cp_ptr, cn_ptr, summary_ptr,
                                                       areas_ptr, stream))
+
+    # train/test splits ------------------------------------------------------------------------------
+    def cell_select(self, seed: int, seeding: int, lb: float, ub: float, complement: bool, rows_ptr):
+        """Host-pointer form (psgd_cell_select): (counts, nnz) per registered partition of
+        cell(lb, ub, complement); the kept row indices go to the device int32 array at rows_ptr."""
+        import numpy as np
+        nparts, _ = self.num_partitions()
+        counts = np.zeros(max(nparts, 1), dtype=np.int64)
+        nnz = np.zeros(max(nparts, 1), dtype=np.int64)
+        check(self._L.psgd_cell_select(self.handle, _java_long(seed), int(seeding), float(lb), float(ub),
+                                       1 if complement else 0, rows_ptr, counts.ctypes.data, nnz.ctypes.data))
+        return counts[:nparts], nnz[:nparts]
+
+    def cell_select_device(self, seed: int, seeding: int, lb: float, ub: float, complement: bool, rows_ptr,
+                           counts_ptr, nnz_ptr=None, stream=None):
+        """psgd_cell_select_device: enqueued on `stream`; counts[n_parts] and nnz[n_parts] on the device."""
+        check(self._L.psgd_cell_select_device(self.handle, _java_long(seed), int(seeding), float(lb), float(ub),
+                                              1 if complement else 0, rows_ptr, counts_ptr, nnz_ptr, stream))
+
+    def gather_dense_device(self, rows_ptr, counts, ld_out: int, x_ptrs, label_ptrs, stream=None):
+        """psgd_gather_dense_device: counts a host int64 array, x_ptrs / label_ptrs the per-partition
+        device addresses (0 where nothing is kept)."""
+        import numpy as np
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        xs = np.ascontiguousarray(x_ptrs, dtype=np.uint64)
+        ys = np.ascontiguousarray(label_ptrs, dtype=np.uint64)
+        check(self._L.psgd_gather_dense_device(self.handle, rows_ptr, counts.ctypes.data, int(ld_out), xs.ctypes.data,
+                                               ys.ctypes.data, stream))
+
+    def gather_csr_device(self, rows_ptr, counts, nnz, label_ptrs, row_ptr_ptrs, col_ptrs, val_ptrs, stream=None):
+        """psgd_gather_csr_device: counts / nnz host int64 arrays, the rest per-partition device addresses."""
+        import numpy as np
+        counts = np.ascontiguousarray(counts, dtype=np.int64)
+        nnz = np.ascontiguousarray(nnz, dtype=np.int64)
+        a = [np.ascontiguousarray(v, dtype=np.uint64) for v in (label_ptrs, row_ptr_ptrs, col_ptrs, val_ptrs)]
+        check(self._L.psgd_gather_csr_device(self.handle, rows_ptr, counts.ctypes.data, nnz.ctypes.data,
+                                             a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data,
+                                             stream))
+
+
+def _java_long(v: int) -> int:
+    """v wrapped to a Java Long (two's complement, 64 bits)."""
+    v = int(v) & 0xFFFFFFFFFFFFFFFF
+    return v - (1 << 64) if v >= 1 << 63 else v

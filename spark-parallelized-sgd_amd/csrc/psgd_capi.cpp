@@ -461,6 +461,11 @@ struct psgd_ctx {
     // binary classification metrics (psgd_binary_counts*): the sort's pair buffers and tile tables
     // (with a table of the call's own and the model forms' margins), and the host-pointer forms' staging
     DevBuf mscratch, mio;
+    // train/test splits (psgd_cell_select* / psgd_gather_*_device): the partitions' global indices
+    // [P] and first-row offsets [P + 1] as uploaded with the descriptors, the host-pointer form's
+    // staging of counts and nnz, and a compaction's table with the CSR tiles' sums
+    DevBuf cidx, csel, stab;
+    std::vector<int64_t> row_off;
 };
 
 namespace {
@@ -643,6 +648,9 @@ int32_t upload_descs(psgd_ctx* ctx, hipStream_t st) {
     HIP_TRY(ctx->descs.ensure(std::max<size_t>(P, 1) * sizeof(psgd::ChainDesc)));
     HIP_TRY(ctx->eparts.ensure((P + 1) * sizeof(psgd::EvalPart)));
     HIP_TRY(ctx->stile0.ensure((P + 1) * sizeof(int64_t)));
+    HIP_TRY(ctx->cidx.ensure((2 * P + 1) * sizeof(int64_t)));
+    std::vector<int64_t> cix(2 * P + 1, 0);   // {partition index [P], first-row offset [P + 1]}
+    size_t ci = 0;
     std::vector<int64_t> st0;
     st0.reserve(P + 1);
     psgd::StatGeom gm{};
@@ -663,6 +671,9 @@ int32_t upload_descs(psgd_ctx* ctx, hipStream_t st) {
         c.ld = q.ld;
         c.rows = nullptr;   // every row (sampled epochs get descriptors of their own)
         h.push_back(c);
+        cix[ci] = kv.first;
+        cix[P + ci + 1] = cix[P + ci] + q.n_rows;
+        ++ci;
         psgd::EvalPart e;
         e.tile0 = tiles;
         psgd::eval_geometry(q.layout, q.ld * (int64_t)dtype_size(q.dtype), q.max_nnz, &e.tile_rows, &e.group);
@@ -675,12 +686,14 @@ int32_t upload_descs(psgd_ctx* ctx, hipStream_t st) {
     ep.push_back(psgd::EvalPart{tiles, 1, 64});
     st0.push_back(stiles);
     HIP_TRY(hipMemcpyAsync(ctx->stile0.p, st0.data(), st0.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ctx->cidx.p, cix.data(), cix.size() * sizeof(int64_t), hipMemcpyHostToDevice, st));
     if (P) HIP_TRY(hipMemcpyAsync(ctx->descs.p, h.data(), P * sizeof(psgd::ChainDesc), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(ctx->eparts.p, ep.data(), ep.size() * sizeof(psgd::EvalPart), hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     ctx->eval_parts = ep;
     ctx->stat_tile0 = st0;
     ctx->stat_geom = gm;
+    ctx->row_off.assign(cix.begin() + (ptrdiff_t)P, cix.end());
     ctx->descs_dirty = false;
     return PSGD_OK;
 }
@@ -824,7 +837,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->eparts, &ctx->etiles, &ctx->epart, &ctx->ew, &ctx->emargins,
                           &ctx->stile0, &ctx->srec, &ctx->sio,
                           &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
-                          &ctx->mscratch, &ctx->mio,
+                          &ctx->mscratch, &ctx->mio, &ctx->cidx, &ctx->csel, &ctx->stab,
                           &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
@@ -2245,6 +2258,195 @@ int32_t psgd_transform_columns(psgd_ctx* ctx, const double* shift, const double*
     if (rc) return rc;
     DeviceGuard g(ctx->device);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+// ---- Train/test splits (cell_select in psgd_kernels.hip, the gathers in psgd_datasplit.hip) ----
+// The same place in the context as the scoring calls: score_prepare, scratch of their own, no
+// epoch state touched. The sampler seeds are derived on the device from the partition indices the
+// descriptor upload left there, so the selection enqueues without a host synchronisation.
+
+static int32_t cell_args(int32_t seeding, double lb, double ub) {
+    if (seeding != PSGD_SEED_PLUS_INDEX && seeding != PSGD_SEED_PARTITIONWISE)
+        return fail(PSGD_EINVAL, "unknown seeding " + std::to_string(seeding));
+    if (lb != lb || ub != ub) return fail(PSGD_EINVAL, "requirement failed: the cell's bounds must not be NaN");
+    return PSGD_OK;
+}
+
+int32_t psgd_cell_select_device(psgd_ctx* ctx, int64_t seed, int32_t seeding, double lb, double ub,
+                                int32_t complement, int32_t* d_rows, int64_t* d_counts, int64_t* d_nnz,
+                                void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = cell_args(seeding, lb, ub);
+    if (rc) return rc;
+    if (!d_counts) return fail(PSGD_EINVAL, "d_counts is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    int64_t n_max = 0, n_total = 0;
+    for (auto& kv : ctx->parts) {
+        n_max = std::max(n_max, kv.second.n_rows);
+        n_total += kv.second.n_rows;
+    }
+    // the kept rows' indices are int32
+    if (n_max > (int64_t)INT32_MAX)
+        return fail(PSGD_EUNSUPPORTED, "a split of a partition of more than 2^31 - 1 rows");
+    if (n_total > 0 && !d_rows) return fail(PSGD_EINVAL, "d_rows is null");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const int P = (int)ctx->parts.size();
+    const int e = psgd::launch_cell_select(ctx->descs.as<psgd::ChainDesc>(), ctx->cidx.as<int64_t>(),
+                                           ctx->cidx.as<int64_t>() + P, P, ctx->parts.begin()->second.layout, seed,
+                                           seeding, lb, ub, complement ? 1 : 0, d_rows, d_counts, d_nnz, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("cell selection launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_cell_select(psgd_ctx* ctx, int64_t seed, int32_t seeding, double lb, double ub, int32_t complement,
+                         int32_t* d_rows, int64_t* counts, int64_t* nnz) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = cell_args(seeding, lb, ub);
+    if (rc) return rc;
+    if (!counts) return fail(PSGD_EINVAL, "counts is null");
+    size_t P = 0;
+    int64_t* d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        P = ctx->parts.size();
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->csel.ensure(2 * P * sizeof(int64_t)));
+        d_out = ctx->csel.as<int64_t>();
+    }
+    rc = psgd_cell_select_device(ctx, seed, seeding, lb, ub, complement, d_rows, d_out, d_out + P, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    std::vector<int64_t> h(2 * P);
+    HIP_TRY(hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(counts, h.data(), P * sizeof(int64_t));
+    if (nnz) std::memcpy(nnz, h.data() + P, P * sizeof(int64_t));
+    return PSGD_OK;
+}
+
+// The table of a compaction (ctx->mu held, score_prepare done): one SplitPart a partition plus the
+// closing entry, uploaded to ctx->stab with room for `extra` int64 behind it (*d_extra). Waits once
+// for the table to leave the host vector.
+static int32_t gather_table(psgd_ctx* ctx, int layout, const int32_t* d_rows, const int64_t* counts, int tile_rows,
+                            void* const* x_out, double* const* y_out, int64_t* const* row_ptr_out,
+                            int32_t* const* col_out, bool extra_tiles, hipStream_t st, int64_t* n_tiles,
+                            int64_t** d_extra) {
+    const size_t P = ctx->parts.size();
+    std::vector<psgd::SplitPart> tab(P + 1);
+    int64_t tiles = 0;
+    size_t c = 0;
+    for (auto& kv : ctx->parts) {
+        const Part& q = kv.second;
+        const int64_t m = counts[c];
+        if (m < 0 || m > q.n_rows)
+            return fail(PSGD_EINVAL, "counts[" + std::to_string(c) + "] = " + std::to_string(m) +
+                                         " is not within the partition's " + std::to_string(q.n_rows) + " rows");
+        // (CSR: col / val may be null where the kept rows hold no non-zero at all)
+        if (m > 0 && (!y_out[c] || (layout == psgd::kDense && !x_out[c])))
+            return fail(PSGD_EINVAL, "an output pointer of partition " + std::to_string(kv.first) + " is null");
+        if (layout == psgd::kCsr && !row_ptr_out[c])
+            return fail(PSGD_EINVAL, "d_row_ptr_out of partition " + std::to_string(kv.first) + " is null");
+        if (layout == psgd::kDense && ((uintptr_t)x_out[c] % 16) != 0)
+            return fail(PSGD_EINVAL, "output rows must be 16-byte aligned");
+        psgd::SplitPart& s = tab[c];
+        s.tile0 = tiles;
+        s.m = m;
+        s.rows = d_rows ? d_rows + ctx->row_off[c] : nullptr;
+        s.x = x_out[c];
+        s.y = y_out[c];
+        s.row_ptr = row_ptr_out ? row_ptr_out[c] : nullptr;
+        s.col = col_out ? col_out[c] : nullptr;
+        tiles += (m + tile_rows - 1) / tile_rows;
+        ++c;
+    }
+    tab[P] = psgd::SplitPart{tiles, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t tab_bytes = (tab.size() * sizeof(psgd::SplitPart) + 255) & ~(size_t)255;
+    HIP_TRY(ctx->stab.ensure(tab_bytes + (extra_tiles ? (size_t)std::max<int64_t>(tiles, 1) * sizeof(int64_t) : 0)));
+    HIP_TRY(hipMemcpyAsync(ctx->stab.p, tab.data(), tab.size() * sizeof(psgd::SplitPart), hipMemcpyHostToDevice, st));
+    // the table leaves a host vector of this call: wait for the copy
+    HIP_TRY(hipStreamSynchronize(st));
+    *n_tiles = tiles;
+    if (d_extra) *d_extra = reinterpret_cast<int64_t*>(ctx->stab.as<char>() + tab_bytes);
+    return PSGD_OK;
+}
+
+int32_t psgd_gather_dense_device(psgd_ctx* ctx, const int32_t* d_rows, const int64_t* counts, int64_t ld_out,
+                                 void* const* d_x_out, double* const* d_labels_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!counts || !d_x_out || !d_labels_out) return fail(PSGD_EINVAL, "counts/d_x_out/d_labels_out are null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const Part& first = ctx->parts.begin()->second;
+    if (first.layout != psgd::kDense) return fail(PSGD_EINVAL, "the registered partitions hold CSR rows");
+    const size_t es = dtype_size(first.dtype);
+    if (ld_out < first.d || ((size_t)ld_out * es) % 16 != 0)
+        return fail(PSGD_EINVAL, "need ld_out >= d and 16-byte aligned rows (ld_out * sizeof(dtype) % 16 == 0)");
+    int64_t kept = 0;
+    for (size_t c = 0; c < ctx->parts.size(); ++c) kept += counts[c] > 0 ? counts[c] : 0;
+    if (kept > 0 && !d_rows) return fail(PSGD_EINVAL, "d_rows is null");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int32_t rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const int tile_rows = psgd::gather_tile_rows(psgd::kDense, ld_out * (int64_t)es);
+    int64_t n_tiles = 0;
+    rc = gather_table(ctx, psgd::kDense, d_rows, counts, tile_rows, d_x_out, d_labels_out, nullptr, nullptr, false, st,
+                      &n_tiles, nullptr);
+    if (rc) return rc;
+    const int e = psgd::launch_gather_dense(ctx->descs.as<psgd::ChainDesc>(), ctx->stab.as<psgd::SplitPart>(),
+                                            (int)ctx->parts.size(), n_tiles, tile_rows, first.d,
+                                            first.dtype == PSGD_F32 ? 1 : 0, ld_out, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("dense gather launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_gather_csr_device(psgd_ctx* ctx, const int32_t* d_rows, const int64_t* counts, const int64_t* nnz,
+                               double* const* d_labels_out, int64_t* const* d_row_ptr_out,
+                               int32_t* const* d_col_out, void* const* d_val_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!counts || !nnz || !d_labels_out || !d_row_ptr_out || !d_col_out || !d_val_out)
+        return fail(PSGD_EINVAL, "counts, nnz or an output pointer array is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const Part& first = ctx->parts.begin()->second;
+    if (first.layout != psgd::kCsr) return fail(PSGD_EINVAL, "the registered partitions hold dense rows");
+    int64_t kept = 0, max_nnz = 0;
+    size_t c = 0;
+    for (auto& kv : ctx->parts) {
+        kept += counts[c] > 0 ? counts[c] : 0;
+        max_nnz = std::max(max_nnz, kv.second.max_nnz);
+        if (nnz[c] < 0 || (nnz[c] > 0 && (!d_col_out[c] || !d_val_out[c])))
+            return fail(PSGD_EINVAL, "d_col_out / d_val_out of partition " + std::to_string(kv.first) +
+                                         " are null for " + std::to_string(nnz[c]) + " non-zeros");
+        ++c;
+    }
+    if (kept > 0 && !d_rows) return fail(PSGD_EINVAL, "d_rows is null");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    int32_t rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const int tile_rows = psgd::gather_tile_rows(psgd::kCsr, 0);
+    int64_t n_tiles = 0;
+    int64_t* tile_sum = nullptr;
+    rc = gather_table(ctx, psgd::kCsr, d_rows, counts, tile_rows, d_val_out, d_labels_out, d_row_ptr_out, d_col_out,
+                      true, st, &n_tiles, &tile_sum);
+    if (rc) return rc;
+    const int e = psgd::launch_gather_csr(ctx->descs.as<psgd::ChainDesc>(), ctx->stab.as<psgd::SplitPart>(),
+                                          (int)ctx->parts.size(), n_tiles, first.dtype == PSGD_F32 ? 1 : 0, max_nnz,
+                                          tile_sum, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("CSR gather launch failed: ") + hipGetErrorString((hipError_t)e));
     return PSGD_OK;
 }
 

@@ -289,4 +289,42 @@ int launch_metrics_keys(const MetricsBufs& B, const double* scores, const double
 int launch_metrics_finish(const MetricsBufs& B, int64_t n, double* thresholds, int64_t* cum_pos, int64_t* cum_neg,
                           int64_t* summary, double* areas, hipStream_t st);
 
+// ---- Train/test splits (cell_select in psgd_kernels.hip; the gathers in psgd_datasplit.hip) ----
+// BernoulliCellSampler over every registered partition: one XORShiftRandom draw x_t per row t in
+// iterator order, row t kept when lb <= x_t < ub (complement: x_t < lb || x_t >= ub). The sampler's
+// seed of descs[c] is derived on the device from its global partition index part_index[c]: seeding
+// 0 = seed + index (wrapping, randomSplit), 1 = the index-th java.util.Random(seed).nextLong()
+// (PartitionwiseSampledRDD, kFold); both go through hashSeed. The kept rows' indices, increasing,
+// are written from rows + row_off[c] on; counts[c] their number; nnz[c] (nullable) the sum of
+// their CSR row lengths (0 for dense rows). Partitions of at most INT32_MAX rows.
+int launch_cell_select(const ChainDesc* descs, const int64_t* part_index, const int64_t* row_off, int n_parts,
+                       int layout, int64_t seed, int seeding, double lb, double ub, int complement, int32_t* rows,
+                       int64_t* counts, int64_t* nnz, hipStream_t st);
+
+// One partition of a compaction: its m kept rows (indices rows[0 .. m), increasing) go to the
+// caller's buffers -- x [m * ld_out] dense rows or the CSR values, y [m] labels, row_ptr [m + 1]
+// and col for CSR. The kept rows are cut into tiles of tile_rows rows, numbered from tile0 on
+// across the partitions in partition-index order; entry n_parts closes the list (its tile0 is the
+// number of tiles).
+struct SplitPart {
+    int64_t tile0;
+    int64_t m;
+    const int32_t* rows;
+    void* x;
+    double* y;
+    int64_t* row_ptr;
+    int32_t* col;
+};
+// Kept rows a tile holds: dense by the output row's bytes (a tile moves about 64 KiB), CSR 256.
+int gather_tile_rows(int layout, int64_t row_bytes);
+// Dense: row k of partition p's output = row rows[k] of descs[p] at the output pitch ld_out
+// (elements; a multiple of 16 bytes, >= d), columns [d, ld_out) zeros; the labels with them.
+int launch_gather_dense(const ChainDesc* descs, const SplitPart* tab, int n_parts, int64_t n_tiles, int tile_rows,
+                        int d, int storage, int64_t ld_out, int num_cus, hipStream_t st);
+// CSR: row_ptr[0 .. m] = the exclusive scan of the kept rows' lengths (from 0), col / val the kept
+// rows' segments back to back, the labels with them. tile_sum [n_tiles] is scratch. max_nnz: the
+// longest registered row (lanes per row).
+int launch_gather_csr(const ChainDesc* descs, const SplitPart* tab, int n_parts, int64_t n_tiles, int storage,
+                      int64_t max_nnz, int64_t* tile_sum, int num_cus, hipStream_t st);
+
 }  // namespace psgd

@@ -1292,6 +1292,123 @@ int launch_sample(const ChainDesc* base, ChainDesc* out, const uint64_t* xs_stat
     return (int)hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------
+// BernoulliCellSampler over the registered partitions (randomSplit, kFold): one
+// nextDouble per row in iterator order, no gap sampling, so the filter branch of sample_kernel
+// with a cell test in place of `<= fraction`. The partition's sampler seed is derived here from
+// its global partition index (the host computes nothing): seed + index, or the index-th nextLong
+// of java.util.Random(seed) reached by composing the LCG's step with itself (x -> A x + C mod
+// 2^48, 2 steps a nextLong), then hashSeed (MurmurHash3 of the Long's 8 big-endian bytes and 56
+// zeros, as sampling::xorshift_hash_seed in psgd_capi.cpp). Integer arithmetic and comparisons
+// only; every output is placed by an exclusive scan, no atomics.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t cell_rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
+
+__device__ uint64_t cell_hash_seed(int64_t s) {
+    uint32_t h = 0x3c074a61u;   // MurmurHash3.arraySeed
+#pragma unroll 1
+    for (int i = 0; i < 16; ++i) {
+        // little-endian words of the big-endian Long followed by 56 zero bytes
+        uint32_t k = i < 2 ? __builtin_bswap32((uint32_t)((uint64_t)s >> (32 - 32 * i))) : 0u;
+        k *= 0xcc9e2d51u;
+        k = cell_rotl32(k, 15);
+        k *= 0x1b873593u;
+        h ^= k;
+        h = cell_rotl32(h, 13);
+        h = h * 5u + 0xe6546b64u;
+    }
+    h ^= 64u;
+    h ^= h >> 16;
+    h *= 0x85ebca6bu;
+    h ^= h >> 13;
+    h *= 0xc2b2ae35u;
+    h ^= h >> 16;
+    return (uint64_t)(int64_t)(int32_t)h;
+}
+
+// The p-th (0-based) nextLong of java.util.Random(seed).
+__device__ int64_t cell_java_long(int64_t seed, int64_t p) {
+    constexpr uint64_t M = (1ull << 48) - 1;
+    uint64_t x = ((uint64_t)seed ^ 0x5DEECE66Dull) & M;
+    uint64_t a = 0x5DEECE66Dull, c = 0xBull, acc_a = 1, acc_c = 0;
+#pragma unroll 1
+    for (uint64_t n = 2 * (uint64_t)p; n; n >>= 1) {
+        if (n & 1) {
+            acc_a = (acc_a * a) & M;
+            acc_c = (acc_c * a + c) & M;
+        }
+        c = ((a + 1) * c) & M;
+        a = (a * a) & M;
+    }
+    x = (acc_a * x + acc_c) & M;
+    x = (x * 0x5DEECE66Dull + 0xBull) & M;
+    const int64_t hi = (int32_t)(uint32_t)(x >> 16);
+    x = (x * 0x5DEECE66Dull + 0xBull) & M;
+    const int64_t lo = (int32_t)(uint32_t)(x >> 16);
+    return (int64_t)(((uint64_t)hi << 32) + (uint64_t)lo);
+}
+
+__global__ __launch_bounds__(kSampThreads) void cell_select_kernel(const ChainDesc* __restrict__ base,
+                                                                   const int64_t* __restrict__ part_index,
+                                                                   const int64_t* __restrict__ row_off, int csr,
+                                                                   int64_t seed, int seeding, double lb, double ub,
+                                                                   int complement, int32_t* __restrict__ rows,
+                                                                   int64_t* __restrict__ counts,
+                                                                   int64_t* __restrict__ nnz) {
+    __shared__ int64_t sh[kSampThreads];
+    const int c = blockIdx.x;
+    const int tid = threadIdx.x;
+    const ChainDesc dsc = base[c];
+    const int64_t nr = dsc.n_rows;
+    const int64_t p = part_index[c];
+    const int64_t sp = seeding == 0 ? (int64_t)((uint64_t)seed + (uint64_t)p) : cell_java_long(seed, p);
+    uint64_t st = cell_hash_seed(sp);
+#pragma unroll 1
+    for (int k = 0; k < 8; ++k)
+        if ((tid >> k) & 1) st = gf2_apply(kSampleJumps.j[k], st);
+    constexpr int64_t kRound = (int64_t)kSampThreads * kSampDraws;
+    int32_t* r = rows + row_off[c];
+    const int64_t* rp = csr ? dsc.row_ptr : nullptr;
+    const bool comp = complement != 0;
+    int64_t m = 0, len = 0;
+    for (int64_t draw0 = 0; draw0 < nr; draw0 += kRound) {
+        uint64_t s = st;
+        uint64_t keep = 0;
+        const int64_t t0 = draw0 + (int64_t)tid * kSampDraws;
+        for (int j = 0; j < kSampDraws; ++j) {
+            const double x = xs_next_double(s);
+            const bool in = x >= lb && x < ub;
+            if (in != comp && t0 + j < nr) keep |= 1ull << j;
+        }
+        int64_t total;
+        int64_t o = m + block_excl_scan(__popcll(keep), sh, &total);
+        while (keep) {
+            const int j = __ffsll((unsigned long long)keep) - 1;
+            keep &= keep - 1;
+            r[o] = (int32_t)(t0 + j);
+            if (rp) len += rp[t0 + j + 1] - rp[t0 + j];
+            ++o;
+        }
+        m += total;
+        st = gf2_apply(kSampleJumps.j[8], st);
+    }
+    int64_t total_len;
+    block_excl_scan(len, sh, &total_len);
+    if (tid == 0) {
+        counts[c] = m;
+        if (nnz) nnz[c] = total_len;
+    }
+}
+
+int launch_cell_select(const ChainDesc* descs, const int64_t* part_index, const int64_t* row_off, int n_parts,
+                       int layout, int64_t seed, int seeding, double lb, double ub, int complement, int32_t* rows,
+                       int64_t* counts, int64_t* nnz, hipStream_t st) {
+    if (n_parts <= 0) return 0;
+    hipLaunchKernelGGL(cell_select_kernel, dim3((unsigned)n_parts), dim3(kSampThreads), 0, st, descs, part_index,
+                       row_off, layout == kCsr ? 1 : 0, seed, seeding, lb, ub, complement, rows, counts, nnz);
+    return (int)hipGetLastError();
+}
+
 int launch_steps(double step, int64_t n, double* steps, hipStream_t stream) {
     if (n <= 0) return 0;
     const int threads = 256;

@@ -660,6 +660,124 @@ class HipEngine(ShardedEngine):
         return out[:-1], regVal
 
 
+    # train/test splits (psgd_cell_select_device / psgd_gather_*_device; split.py) ------------------
+    def _storage_dtype(self):
+        """The torch dtype the context stores this data's rows in (f64 when it holds no partition)."""
+        torch = self.torch
+        for part in self._data.partitions:
+            v = part.x if isinstance(part, (DensePartition, DevicePartition)) else part.val
+            if torch.is_tensor(v):
+                return v.dtype
+            return torch.float32 if v.dtype == np.float32 else torch.float64
+        return torch.float64
+
+    def _cell_select(self, lb, ub, complement, seed, seeding):
+        """cell(lb, ub, complement) over this rank's partitions (self.stream current, ctx.engine_lock
+        held): (rows, offsets, counts, nnz) -- the device index array, each local partition's first
+        entry in it, and the host counts after the one read-back."""
+        torch = self.torch
+        if self.n_local > 0 and self.ctx.registered_token != self._key:
+            self._register(self._data)
+        n_rows = [self._data.partitions[p].n_rows for p in range(self.lo, self.hi)]
+        offs = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
+        rows = torch.empty(max(int(offs[-1]), 1), dtype=torch.int32, device=self.dev)
+        cn = torch.zeros(2 * max(self.n_local, 1), dtype=torch.int64, device=self.dev)
+        if self.n_local > 0:
+            self.ctx.cell_select_device(seed, seeding, lb, ub, complement, rows.data_ptr(), cn.data_ptr(),
+                                        cn.data_ptr() + 8 * self.n_local, self.stream.cuda_stream)
+        h = cn.cpu().numpy()
+        return rows, offs, h[: self.n_local].copy(), h[self.n_local: 2 * self.n_local].copy()
+
+    def cell_rows(self, lb: float, ub: float, complement: bool, seed: int, seeding: int):
+        """The row indices BernoulliCellSampler(lb, ub, complement) keeps of each of this rank's
+        partitions, in partition order: a list of int32 device tensors, increasing (include/psgd.h has
+        the semantics; seeding is N.SEED_PLUS_INDEX for randomSplit, N.SEED_PARTITIONWISE for kFold)."""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            with self.ctx.engine_lock:
+                rows, offs, counts, _ = self._cell_select(lb, ub, complement, seed, seeding)
+            out = [rows[int(offs[i]): int(offs[i]) + int(counts[i])] for i in range(self.n_local)]
+        caller.wait_stream(self.stream)
+        rows.record_stream(caller)
+        return out
+
+    def split_cell(self, lb: float, ub: float, complement: bool, seed: int, seeding: int) -> PartitionedData:
+        """The rows of cell(lb, ub, complement) as a PartitionedData of device partitions: the
+        selection, one read-back of the counts, torch tensors for the outputs (one arena a split, the
+        partitions are views of it) and one compaction launch over all partitions. It lists all P
+        partitions; this rank's block is filled, empty device placeholders stand for the others';
+        `partition_counts` holds every partition's row count, all-gathered, on every rank. The rows
+        come from the context's registered copy: a source column_transform is in them, the result
+        carries none."""
+        torch = self.torch
+        data, P, d = self._data, self._data.num_partitions, self._data.num_features
+        csr = any(isinstance(q, (CsrPartition, DeviceCsrPartition)) for q in data.partitions)
+        sdt = self._storage_dtype()
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            with self.ctx.engine_lock:
+                rows, offs, counts, nnz = self._cell_select(lb, ub, complement, seed, seeding)
+                m0 = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64)
+                M = int(m0[-1])
+                y = torch.empty(M, dtype=torch.float64, device=self.dev)
+                ys = [y[int(m0[i]): int(m0[i + 1])] for i in range(self.n_local)]
+                if csr:
+                    z0 = np.concatenate([[0], np.cumsum(nnz, dtype=np.int64)]).astype(np.int64)
+                    rp = torch.empty(M + max(self.n_local, 1), dtype=torch.int64, device=self.dev)
+                    col = torch.empty(int(z0[-1]), dtype=torch.int32, device=self.dev)
+                    val = torch.empty(int(z0[-1]), dtype=sdt, device=self.dev)
+                    rps = [rp[int(m0[i]) + i: int(m0[i + 1]) + i + 1] for i in range(self.n_local)]
+                    cols = [col[int(z0[i]): int(z0[i + 1])] for i in range(self.n_local)]
+                    vals = [val[int(z0[i]): int(z0[i + 1])] for i in range(self.n_local)]
+                    if self.n_local > 0:
+                        ptr = lambda ts: [t.data_ptr() if t.numel() else 0 for t in ts]
+                        self.ctx.gather_csr_device(rows.data_ptr(), counts, nnz, ptr(ys), [t.data_ptr() for t in rps],
+                                                   ptr(cols), ptr(vals), self.stream.cuda_stream)
+                    local = [DeviceCsrPartition(ys[i], rps[i], cols[i], vals[i], d) for i in range(self.n_local)]
+                    arena = (y, rp, col, val)
+                    zero = torch.zeros(1, dtype=torch.int64, device=self.dev)
+                    empty = lambda: DeviceCsrPartition(y[:0], zero, col[:0], val[:0], d)
+                else:
+                    vec = 4 if sdt == torch.float32 else 2
+                    ld = (d + vec - 1) // vec * vec
+                    X = torch.empty((M, ld), dtype=sdt, device=self.dev)
+                    xs = [X[int(m0[i]): int(m0[i + 1])] for i in range(self.n_local)]
+                    if self.n_local > 0:
+                        ptr = lambda ts: [t.data_ptr() if t.numel() else 0 for t in ts]
+                        self.ctx.gather_dense_device(rows.data_ptr(), counts, ld, ptr(xs), ptr(ys),
+                                                     self.stream.cuda_stream)
+                    local = [DevicePartition(ys[i], xs[i], d) for i in range(self.n_local)]
+                    arena = (y, X)
+                    empty = lambda: DevicePartition(y[:0], X[:0], d)
+            part_counts = np.zeros(P, dtype=np.int64)
+            if self.world > 1:
+                import torch.distributed as dist
+                shards = [shard_range(P, r, self.world) for r in range(self.world)]
+                width = max(max(hi - lo for lo, hi in shards), 1)
+                buf = torch.zeros(width, dtype=torch.int64, device=self.dev)
+                buf[: self.n_local].copy_(torch.from_numpy(counts))
+                got = torch.empty(self.world * width, dtype=torch.int64, device=self.dev)
+                if dist.get_backend() == "gloo":
+                    dist.all_gather(list(got.view(self.world, width).unbind(0)), buf)
+                else:
+                    dist.all_gather_into_tensor(got, buf)
+                h = got.cpu().numpy().reshape(self.world, width)
+                for r, (lo, hi) in enumerate(shards):
+                    part_counts[lo:hi] = h[r, : hi - lo]
+            else:
+                part_counts[self.lo: self.hi] = counts
+        caller.wait_stream(self.stream)
+        for t in arena:
+            t.record_stream(caller)
+        parts = [empty() for _ in range(self.lo)] + local + [empty() for _ in range(P - self.hi)]
+        out = PartitionedData(parts)
+        out.partition_counts = part_counts
+        return out
+
+
 def merge_gradient_sums(rows):
     """Rows of {gradientSum[d], lossSum, count}, one a rank, added in row order: ((r0 + r1) + r2) + ..
     (host arrays or device tensors)."""
