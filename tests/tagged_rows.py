@@ -285,7 +285,7 @@ def _row(data, r, T):
 
 
 def chain(data, seq, w_in, grad, upd, step, reg, dtype=np.float64, order=0, mutate=None, at=None,
-          beta=0.9, gamma=0.999, eps=1e-8, stale_trace=False):
+          beta=0.9, gamma=0.999, eps=1e-8, stale_trace=False, read=None):
     """ParallelizedSGD's chain (gradient, updater, iter += 1 per sample; no per-sample test: the
     caller truncates `seq` where the oracle breaks) over rows `seq` in order, every operation in
     `dtype`: the three binary gradients, the multinomial LogisticGradient (data["K"] > 2) and the
@@ -294,6 +294,11 @@ def chain(data, seq, w_in, grad, upd, step, reg, dtype=np.float64, order=0, muta
     mutate (at = position in seq) makes one row wrong: "step_late" takes iter + 1 for it, "swap"
     processes it after its successor, "stale" computes its margin from the weights before the
     previous update, "drop" does not apply it, "dup" applies it twice.
+
+    read (binary gradients; default None: no effect): read(k, row, idx, wv, w) is called before the
+    margin of position k with the row's columns (None: dense), the weights wv the margin is about to
+    take for them and the whole current vector w, and returns the weights the margin takes: an
+    observer, or a mutation of single reads (tests/reuse_schedule.py).
 
     Returns (w, trace) with trace[k] = (row, iter, z, active, z_stale) per position (z in double;
     z_stale, with stale_trace, the margin the row would get from the weights before the previous
@@ -344,7 +349,10 @@ def chain(data, seq, w_in, grad, upd, step, reg, dtype=np.float64, order=0, muta
                     gi = (np.arange(K - 1)[:, None] * d + idx[None, :]).reshape(-1)
                     g = (mult[:, None] * x[None, :]).reshape(-1)
             else:
-                zz = _dot(x, wm if idx is None else wm[idx], order)
+                wv = wm if idx is None else wm[idx]
+                if read is not None:
+                    wv = read(k, r, idx, wv, w)
+                zz = _dot(x, wv, order)
                 z = float(zz)
                 if stale_trace:
                     z_stale = float(_dot(x, w_prev if idx is None else w_prev[idx], order))
@@ -407,10 +415,11 @@ def fold(ws, counts):
 
 
 def run(data, grad, upd, step, reg, iters=1, fraction=1.0, limits=None, dtype=np.float64, order=0,
-        mutate=None, at=None, stale_trace=False):
+        mutate=None, at=None, stale_trace=False, read=None):
     """`iters` outer iterations of chain() over the partitions and the fold in double, as the
     device does it. limits[p]: the number of rows chain p applies (the oracle's break counts;
-    first iteration only). mutate / at = (chain, position): first iteration only.
+    first iteration only). mutate / at = (chain, position): first iteration only. read[p]: chain()'s
+    `read` for chain p (a dict; first iteration only).
     Returns (folded weights, per-chain weights of the last iteration, traces of the first)."""
     offs = data["offs"]
     w = np.asarray(data["w0"], np.float64)
@@ -423,7 +432,7 @@ def run(data, grad, upd, step, reg, iters=1, fraction=1.0, limits=None, dtype=np
         for p, seq in enumerate(seqs):
             mut = mutate if (mutate and i == 1 and at[0] == p) else None
             wp, tr = chain(data, seq, w, grad, upd, step, reg, dtype, order, mut, at[1] if mut else None,
-                           stale_trace=stale_trace and i == 1)
+                           stale_trace=stale_trace and i == 1, read=read.get(p) if (read and i == 1) else None)
             ws.append(wp.astype(np.float64))
             traces.append(tr)
         first = traces if first is None else first
@@ -667,14 +676,16 @@ def build(pkg, c):
         return _BUILT[c["id"]]
     O = _oracle()
     R = ring_rows(pkg, c)
-    if c["layout"] == "csr":
+    if c.get("make"):
+        data = c["make"](c)     # a case that brings its own generator (tests/reuse_schedule.py)
+    elif c["layout"] == "csr":
         data = csr_data(c["seed"], c["sizes"], c["d"], c["grad"], c["kmin"], c["kmax"], c["n_tags"],
                         storage=np.float32 if c["compute"] == "f32" else np.float64, fraction=c["fraction"],
                         d_shared=c["d_shared"])
     else:
         data = dense_data(c["seed"], c["sizes"], c["d"], c["grad"], c["recipe"], c["storage"], R, c["fraction"],
                           K=c["K"], cover=c["nv"] > 0)
-    if c["grad"] == "hinge":
+    if c["grad"] == "hinge" and not c.get("make"):
         hinge_pivot(data, c)
     mat = matrix(data)
     kw = dict(num_classes=c["K"]) if c["K"] > 2 else {}

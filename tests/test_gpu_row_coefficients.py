@@ -82,7 +82,8 @@ def describe(c, ref, q):
     return where
 
 
-def run_case(pkg, monkeypatch, c, want, name):
+def run_case(pkg, monkeypatch, c, want, name, describe=describe, record=RECORD):
+    """describe, record: another module's failure text and recorder (tests/test_gpu_sparse_reuse.py)."""
     ref = T.build(pkg, c)
     data = ref["data"]
     for k, v in c["env"].items():
@@ -134,7 +135,7 @@ def run_case(pkg, monkeypatch, c, want, name):
         f"{name}: an applied row left its tag at zero: "
         f"{describe(c, ref, int(np.argmax((w[idx] == 0.0) & ~zero & keep)))}")
     S, q = T.statistic(w, _with(wr, idx, expect), scale, idx, keep)
-    RECORD[name] = S
+    record[name] = S
     print(f"{name}: S = {S:.4g} (bar {bar:.4g}) at {describe(c, ref, q)}")
     assert S <= bar, (f"{name}: tag coordinate off by {S:.4g} x its scale (bar {bar:.4g}) at {describe(c, ref, q)}: "
                       f"{w[idx][q]!r} vs {expect[q]!r}")
