@@ -38,6 +38,7 @@
 // ||w||^2 is taken exactly from the registers at every block start (one more wave sum under the
 // dots), so the fp32 recurrence runs over at most 8 rows. The first passing row ends the chain.
 #include "psgd_device.h"
+#include "psgd_dispatch.h"
 
 #include <stdlib.h>
 
@@ -704,12 +705,9 @@ RingPlan block_ring_plan(int nv, bool conv, size_t budget) {
 }
 
 template <typename S, int GRAD, int UPD, int NV, bool CONV>
-static int launch_block(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st,
-                        int* ring = nullptr) {
-    const RingPlan plan = block_ring_plan(NV, CONV, lds > 0 ? lds : (size_t)64 * 1024);
-    const RingGeom g = plan.g;
-    const size_t bytes = plan.bytes;
-    note_ring(ring, g);
+static int launch_block(const ChainLaunch& L, const KParams& kp, bool full, const RingPlan& ring, hipStream_t st) {
+    const RingGeom g = ring.g;
+    const size_t bytes = ring.bytes;
     if (full) {
         auto k = chain_block<S, GRAD, UPD, NV, true, CONV>;
         (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -726,73 +724,20 @@ static int launch_block(const ChainLaunch& L, const KParams& kp, bool full, size
     return (int)hipGetLastError();
 }
 
-// The dispatch over every instantiation (left out of the diagnostic build, tools/chain_bench.hip).
+// The family's entry (left out of the diagnostic build, tools/chain_bench.hip): the plan's fields
+// to the instance. Simple / SquaredL2 only; tol > 0 (plan.conv) is an instance of its own.
 #ifndef PSGD_NO_DISPATCH
-// Variant 300 + 40 (the per-sample break, tol > 0) + NV.
-template <typename S, int GRAD, int UPD, bool CONV>
-static int block_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld,
-                    size_t lds, hipStream_t st, int* variant, int* ring) {
-    constexpr int VEC = 16 / sizeof(S);
-    int nv = 1;
-    while (nv * 64 * VEC < max_ld) nv *= 2;
-    const bool full = min_ld >= (int64_t)nv * 64 * VEC;
-    if (variant) *variant = 300 + (CONV ? 40 : 0) + nv;
-    switch (nv) {
-    case 1: return launch_block<S, GRAD, UPD, 1, CONV>(L, kp, full, lds, st, ring);
-    case 2: return launch_block<S, GRAD, UPD, 2, CONV>(L, kp, full, lds, st, ring);
-    case 4: return launch_block<S, GRAD, UPD, 4, CONV>(L, kp, full, lds, st, ring);
-    case 8: return launch_block<S, GRAD, UPD, 8, CONV>(L, kp, full, lds, st, ring);
-    default: return -3;
-    }
+int launch_block(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    const ChainSpec& s = p.spec;
+    return dispatch_int<1, 0>(s.storage, [&](auto sc) {
+    return dispatch_int<G_LOGISTIC, G_LEAST_SQUARES, G_HINGE>(s.gradient, [&](auto gc) {
+    return dispatch_int<U_SIMPLE, U_SQUARED_L2>(s.updater, [&](auto uc) {
+    return dispatch_bool(p.conv, [&](auto conv) {
+    return dispatch_int<1, 2, 4, 8>(p.nv, [&](auto nv) {
+        return launch_block<FloatOf<decltype(sc)::value>, decltype(gc)::value, decltype(uc)::value,
+                            decltype(nv)::value, decltype(conv)::value>(L, kp, p.full, ring_of_plan(p), st);
+    }); }); }); }); });
 }
-
-template <typename S, int GRAD>
-static int block_upd(const ChainLaunch& L, const KParams& kp, int upd, int64_t min_ld,
-                     int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    const bool conv = kp.tol > 0.0;   // the per-sample break: a template instance of its own
-    if (upd == U_SIMPLE)
-        return conv ? block_nv<S, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
-                    : block_nv<S, GRAD, U_SIMPLE, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    if (upd == U_SQUARED_L2)
-        return conv ? block_nv<S, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
-                    : block_nv<S, GRAD, U_SQUARED_L2, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    return -3;
-}
-
-template <typename S>
-static int block_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, int64_t min_ld,
-                      int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    switch (grad) {
-    case G_LOGISTIC: return block_upd<S, G_LOGISTIC>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
-    case G_LEAST_SQUARES: return block_upd<S, G_LEAST_SQUARES>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
-    case G_HINGE: return block_upd<S, G_HINGE>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
-    default: return -3;
-    }
-}
-
-bool block_path_applies(int layout, int compute, int updater, bool check_conv, int storage,
-                        int64_t max_ld) {
-    // any tol (CONV instances when kp.tol > 0); PSGD_B64_CONV=0 keeps tol > 0 on the per-sample
-    // kernels, as for chain_block64 (read at every launch)
-    if (check_conv) {
-        const char* e = getenv("PSGD_B64_CONV");
-        if (e && e[0] == '0') return false;
-    }
-    const int vec = storage == 1 ? 4 : 2;
-    return layout == kDense && compute == 1 &&
-           (updater == U_SIMPLE || updater == U_SQUARED_L2) && max_ld <= 8 * 64 * vec;
-}
-
-int launch_block_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                        int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                        hipStream_t stream, int* kernel_variant, int* ring) {
-    if (kp.n_chains <= 0) return 0;
-    const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
-    if (storage == 1)
-        return block_grad<float>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
-    return block_grad<double>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
-}
-
 #endif  // PSGD_NO_DISPATCH
 
 }  // namespace psgd

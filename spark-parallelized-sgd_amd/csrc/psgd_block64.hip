@@ -47,6 +47,7 @@
 //                    f64 slot in LDS.
 // No MFMA: the triangle is 3.5 dots per row (an f64 16x16x4 MFMA tile would spend 16).
 #include "psgd_device.h"
+#include "psgd_dispatch.h"
 
 #include <type_traits>
 
@@ -948,12 +949,9 @@ RingPlan block64_ring_plan(int nv, bool conv, size_t budget) {
 }
 
 template <typename S, int GRAD, int UPD, int NV, int H, bool CONV>
-static int launch_block64(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st,
-                          int* ring = nullptr) {
-    const RingPlan plan = block64_ring_plan(NV, CONV, lds > 0 ? lds : (size_t)64 * 1024);
-    const RingGeom g = plan.g;
-    const size_t bytes = plan.bytes;
-    note_ring(ring, g);
+static int launch_block64(const ChainLaunch& L, const KParams& kp, bool full, const RingPlan& ring, hipStream_t st) {
+    const RingGeom g = ring.g;
+    const size_t bytes = ring.bytes;
     const dim3 threads(64 * (3 + H));
     if (full) {
         auto k = chain_block64<S, GRAD, UPD, NV, true, H, CONV>;
@@ -971,89 +969,26 @@ static int launch_block64(const ChainLaunch& L, const KParams& kp, bool full, si
     return (int)hipGetLastError();
 }
 
+// The family's entry (left out of the diagnostic builds, tools/chain_bench64.hip): the plan's
+// fields to the instance. Simple / SquaredL2 only; tol > 0 (plan.conv) is an instance of its own;
+// one chain wave (H = 1) at NV 1, 2, 4, two at NV 2, 4, 8.
 #ifndef PSGD_NO_DISPATCH
-// Two chain waves (H = 2) from NV = 2 on; PSGD_B64_WAVES=1 keeps one where its share of a
-// block fits the registers (NV <= 4; A/B measurements). Variant 700 + 40 (per-sample break) +
-// 10 (H - 1) + NV.
-template <typename S, int GRAD, int UPD, bool CONV>
-static int block64_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld,
-                      size_t lds, hipStream_t st, int* variant, int* ring) {
-    constexpr int VEC = 16 / sizeof(S);
-    static const bool one_wave = [] {
-        const char* e = getenv("PSGD_B64_WAVES");
-        return e && atoi(e) == 1;
-    }();
-    int nv = 1;
-    while (nv * 64 * VEC < max_ld) nv *= 2;
-    const bool full = min_ld >= (int64_t)nv * 64 * VEC;
-    const int H = (nv >= 2 && !(one_wave && nv <= 4)) ? 2 : 1;
-    if (variant) *variant = 700 + (CONV ? 40 : 0) + 10 * (H - 1) + nv;
-    if (H == 1) {
-        switch (nv) {
-        case 1: return launch_block64<S, GRAD, UPD, 1, 1, CONV>(L, kp, full, lds, st, ring);
-        case 2: return launch_block64<S, GRAD, UPD, 2, 1, CONV>(L, kp, full, lds, st, ring);
-        case 4: return launch_block64<S, GRAD, UPD, 4, 1, CONV>(L, kp, full, lds, st, ring);
-        default: return -3;
-        }
-    }
-    switch (nv) {
-    case 2: return launch_block64<S, GRAD, UPD, 2, 2, CONV>(L, kp, full, lds, st, ring);
-    case 4: return launch_block64<S, GRAD, UPD, 4, 2, CONV>(L, kp, full, lds, st, ring);
-    case 8: return launch_block64<S, GRAD, UPD, 8, 2, CONV>(L, kp, full, lds, st, ring);
-    default: return -3;
-    }
+int launch_block64(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    const ChainSpec& s = p.spec;
+    if (s.gradient == G_LOGISTIC && !L.zbuf64) return (int)hipErrorInvalidValue;
+    return dispatch_int<1, 0>(s.storage, [&](auto sc) {
+    return dispatch_int<G_LOGISTIC, G_LEAST_SQUARES, G_HINGE>(s.gradient, [&](auto gc) {
+    return dispatch_int<U_SIMPLE, U_SQUARED_L2>(s.updater, [&](auto uc) {
+    return dispatch_bool(p.conv, [&](auto conv) {
+    return dispatch_int<1, 2>(p.h, [&](auto h) {
+        auto launch = [&](auto nv) {
+            return launch_block64<FloatOf<decltype(sc)::value>, decltype(gc)::value, decltype(uc)::value,
+                                  decltype(nv)::value, decltype(h)::value, decltype(conv)::value>(L, kp, p.full, ring_of_plan(p), st);
+        };
+        if constexpr (decltype(h)::value == 1) return dispatch_int<1, 2, 4>(p.nv, launch);
+        else return dispatch_int<2, 4, 8>(p.nv, launch);
+    }); }); }); }); });
 }
-
-template <typename S, int GRAD>
-static int block64_upd(const ChainLaunch& L, const KParams& kp, int upd, int64_t min_ld,
-                       int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    // the per-sample break (tol > 0, PSGD.scala:262) is a template instance of its own
-    const bool conv = kp.tol > 0.0;
-    if (upd == U_SIMPLE)
-        return conv ? block64_nv<S, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
-                    : block64_nv<S, GRAD, U_SIMPLE, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    if (upd == U_SQUARED_L2)
-        return conv ? block64_nv<S, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant, ring)
-                    : block64_nv<S, GRAD, U_SQUARED_L2, false>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    return -3;
-}
-
-template <typename S>
-static int block64_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, int64_t min_ld,
-                        int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    switch (grad) {
-    case G_LOGISTIC: return block64_upd<S, G_LOGISTIC>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
-    case G_LEAST_SQUARES: return block64_upd<S, G_LEAST_SQUARES>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
-    case G_HINGE: return block64_upd<S, G_HINGE>(L, kp, upd, min_ld, max_ld, lds, st, variant, ring);
-    default: return -3;
-    }
-}
-
-bool block64_path_applies(int layout, int compute, int updater, bool check_conv, int storage,
-                          int64_t max_ld) {
-    // any tol: the per-sample break runs in the block recurrence (CONV instances, kp.tol > 0);
-    // PSGD_B64_CONV=0 sends tol > 0 to the per-sample kernels instead (tests of chain_split's
-    // break path, A/B measurements; read at every launch)
-    if (check_conv) {
-        const char* e = getenv("PSGD_B64_CONV");
-        if (e && e[0] == '0') return false;
-    }
-    const int vec = storage == 1 ? 4 : 2;
-    return layout == kDense && compute == 0 &&
-           (updater == U_SIMPLE || updater == U_SQUARED_L2) && max_ld <= 8 * 64 * vec;
-}
-
-int launch_block64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                          int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                          hipStream_t stream, int* kernel_variant, int* ring) {
-    if (kp.n_chains <= 0) return 0;
-    if (gradient == G_LOGISTIC && !L.zbuf64) return (int)hipErrorInvalidValue;
-    const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
-    if (storage == 1)
-        return block64_grad<float>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
-    return block64_grad<double>(L, kp, gradient, updater, min_ld, max_ld, lds, stream, kernel_variant, ring);
-}
-
 #endif  // PSGD_NO_DISPATCH
 
 }  // namespace psgd

@@ -1309,64 +1309,68 @@ static int32_t run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const 
     L.wstride = 0;
     L.walpha = nullptr;
     L.wnsq0 = nullptr;
-    if (layout == psgd::kCsr && params->compute_dtype == PSGD_F32) {
-        // fp32 working weights of the CSR kernels (one d-vector per chain, HBM/L2-resident, and
-        // 128 + 1024 floats the kernels' masked-off lanes load from / store to)
-        // (rows 256-byte aligned: the epoch's init kernel stores 16-byte vectors)
-        L.wstride = ((int64_t)d + 128 + 1024 + 63) / 64 * 64;
-        HIP_TRY(ctx->wf32.ensure((size_t)P * (size_t)L.wstride * sizeof(float), true));
-        // (the fp32 LDS head of chain_sparse_lds; below it the chains never touch the vector)
-        reroll_vectors(ctx->wf32, L.wstride, P, d, (int)std::max<int64_t>(psgd::sparse_lds_head(d), 0), st);
-        HIP_TRY(ctx->walpha.ensure((size_t)P * sizeof(double)));
-        HIP_TRY(ctx->wnsq0.ensure(sizeof(double)));
-        L.wf32 = ctx->wf32.as<float>();
-        L.walpha = ctx->walpha.as<double>();
-        L.wnsq0 = ctx->wnsq0.as<double>();
-    }
+    // which kernel runs, and the buffers it gets (plan_chains)
+    psgd::ChainSpec spec{};
+    spec.layout = layout;
+    spec.storage = first.dtype == PSGD_F32 ? 1 : 0;
+    spec.compute = params->compute_dtype == PSGD_F32 ? 1 : 0;
+    spec.gradient = params->gradient;
+    spec.updater = params->updater;
+    spec.conv = conv;
+    spec.d = d;
+    spec.nc = mn ? params->num_classes - 1 : 0;
+    spec.min_ld = min_ld;
+    spec.max_ld = max_ld;
+    spec.max_nnz = max_nnz;
+    spec.n_max = n_max;
     // SquaredL2's alpha-scaled CSR kernels need every prefix product of (1 - s_j lambda) in range
-    const bool alpha_ok = params->updater != PSGD_UPDATER_SQUARED_L2 ||
-                          alpha_in_range(ctx, params->step_size, params->reg_param, n_max);
-    if (layout == psgd::kCsr && params->compute_dtype == PSGD_F64 && !mn && !psgd::per_sample_forced() &&
-        (psgd::sparse_lds64_applies(d, max_nnz, params->updater, conv, alpha_ok, n_max) ||
-         psgd::sparse64_path_applies(layout, 0, params->updater, conv, alpha_ok))) {
-        // the fp64 CSR kernels' per-chain f64 vectors (d + 1152 doubles, in L.wf32's memory),
-        // chain_sparse64's alphas, and ||w_in||^2 for the per-sample break. Only when one of those
-        // kernels will run (chain_general keeps its weights in w_out, and C5's
-        // vectors are ~34 GB); if HBM cannot hold them the epoch runs chain_general instead.
-        const int64_t stride = 2 * (((int64_t)d + 128 + 1024 + 63) / 64 * 64);
-        const size_t need = (size_t)P * (size_t)stride * sizeof(float);
+    spec.alpha_ok = params->updater != PSGD_UPDATER_SQUARED_L2 ||
+                    alpha_in_range(ctx, params->step_size, params->reg_param, n_max);
+    spec.lds_budget = lds_spread_bytes(ctx, (size_t)P);
+    spec.f64_vectors_unavailable = false;
+    psgd::ChainPlan plan = psgd::plan_chains(spec);
+    if (plan.vec == psgd::kBufF64) {
+        // the fp64 CSR kernels' per-chain f64 vectors (d + 1152 doubles, in L.wf32's memory): only
+        // when one of those kernels will run (chain_general keeps its weights in
+        // w_out, and C5's vectors are ~34 GB); if HBM cannot hold them the epoch runs
+        // chain_general instead.
+        const size_t need = (size_t)P * (size_t)plan.vec_stride * sizeof(float);
         // (a size that failed once is not retried every epoch -- each retry frees the
         // old buffer and tries the VMM chunks and a hipMalloc of tens of GB again)
-        if (need != ctx->wf64_failed && ctx->wf32.ensure(need, true) == hipSuccess) {
-            // (the fp64 head is shorter than the fp32 one: half of it is inside the fp64 tail)
-            reroll_vectors(ctx->wf32, stride, P, 2 * d, (int)std::max<int64_t>(psgd::sparse_lds_head(d), 0), st);
-            HIP_TRY(ctx->walpha.ensure((size_t)P * sizeof(double)));
-            HIP_TRY(ctx->wnsq0.ensure(sizeof(double)));
-            L.wstride = stride;
-            L.wf32 = ctx->wf32.as<float>();
-            L.walpha = ctx->walpha.as<double>();
-            L.wnsq0 = ctx->wnsq0.as<double>();
-        } else {
+        if (need == ctx->wf64_failed || ctx->wf32.ensure(need, true) != hipSuccess) {
             (void)hipGetLastError();   // the failed allocation is not the epoch's error
             if (need != ctx->wf64_failed)
                 fprintf(stderr, "psgd: the fp64 CSR chains' weight vectors (%zu bytes) do not fit in HBM: "
                         "this epoch and later ones of this size run chain_general (variant 201)\n", need);
             ctx->wf64_failed = need;
+            spec.f64_vectors_unavailable = true;
+            plan = psgd::plan_chains(spec);
         }
+    } else if (plan.vec == psgd::kBufF32) {
+        // fp32 working weights of the CSR kernels (one vector per chain, HBM/L2-resident)
+        HIP_TRY(ctx->wf32.ensure((size_t)P * (size_t)plan.vec_stride * sizeof(float), true));
     }
-    if (params->gradient == PSGD_GRADIENT_LOGISTIC && params->compute_dtype == PSGD_F32 &&
-        layout == psgd::kDense) {
-        // per-row margins of the fp32 Logistic block kernel (its loss is summed after the chain)
-        L.zstride = std::max<int64_t>(n_max, 1);
-        HIP_TRY(ctx->zbuf.ensure((size_t)P * (size_t)L.zstride * sizeof(float)));
-        L.zbuf = ctx->zbuf.as<float>();
+    if (plan.vec != psgd::kBufNone) {
+        L.wstride = plan.vec_stride;
+        // (a fresh buffer may be replaced by a better placed one: before L.wf32 is taken)
+        reroll_vectors(ctx->wf32, L.wstride, P, plan.vec == psgd::kBufF64 ? 2 * d : d, (int)plan.reroll_head, st);
+        L.wf32 = ctx->wf32.as<float>();
     }
-    if (params->gradient == PSGD_GRADIENT_LOGISTIC && params->compute_dtype == PSGD_F64 &&
-        layout == psgd::kDense && !mn) {
-        // per-row dots of the fp64 per-sample kernel (its loss is summed after the chain)
+    if (plan.walpha) {
+        HIP_TRY(ctx->walpha.ensure((size_t)P * sizeof(double)));
+        L.walpha = ctx->walpha.as<double>();
+    }
+    if (plan.wnsq0_buf) {
+        HIP_TRY(ctx->wnsq0.ensure(sizeof(double)));
+        L.wnsq0 = ctx->wnsq0.as<double>();
+    }
+    if (plan.zbuf != psgd::kBufNone) {
+        // per-row margins (fp32) / dots (fp64) of a dense Logistic chain: its loss is summed after it
         L.zstride = std::max<int64_t>(n_max, 1);
-        HIP_TRY(ctx->zbuf.ensure((size_t)P * (size_t)L.zstride * sizeof(double)));
-        L.zbuf64 = ctx->zbuf.as<double>();
+        const bool z64 = plan.zbuf == psgd::kBufF64;
+        HIP_TRY(ctx->zbuf.ensure((size_t)P * (size_t)L.zstride * (z64 ? sizeof(double) : sizeof(float))));
+        if (z64) L.zbuf64 = ctx->zbuf.as<double>();
+        else L.zbuf = ctx->zbuf.as<float>();
     }
     psgd::KParams kp;
     kp.reg = params->reg_param;
@@ -1378,9 +1382,9 @@ static int32_t run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const 
     kp.n_chains = P;
     kp.nc = mn ? params->num_classes - 1 : 0;
     kp.n_max = n_max;
-    kp.alpha_ok = alpha_ok;
+    kp.alpha_ok = spec.alpha_ok;
 
-    int weights_in = psgd::kWeightsOut;   // where the launch left the chains' weights
+    int weights_in = psgd::kWeightsOut;   // where the epoch left the chains' weights
     if (sample_empty) {
         // RDD.sample with fraction 0: every partition is empty -> (w_in, 0, 0, 0) per chain.
         for (int p = 0; p < P; ++p)
@@ -1397,11 +1401,10 @@ static int32_t run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const 
             HIP_TRY(hipEventCreate(&ctx->ev_end[ek]));
         }
         HIP_TRY(hipEventRecord(ctx->ev_begin[ek], st));
-        int e = psgd::launch_chains(L, kp, layout, first.dtype == PSGD_F32 ? 1 : 0,
-                                    params->compute_dtype == PSGD_F32 ? 1 : 0, params->gradient,
-                                    params->updater, conv, min_ld, max_ld,
-                                    lds_spread_bytes(ctx, (size_t)P), st, &ctx->last_variant, max_nnz,
-                                    &weights_in, ctx->last_ring);
+        int e = psgd::launch_chains(L, kp, plan, st);
+        weights_in = plan.weights_in;
+        ctx->last_variant = plan.variant;
+        for (int k = 0; k < 4; ++k) ctx->last_ring[k] = plan.ring[k];
         HIP_TRY(hipEventRecord(ctx->ev_end[ek], st));
         if (e == 0) ++ctx->chain_launches;
         if (L.stamps) {   // PSGD_STAMPS=1: per-chain cycle counters of the CSR fp32 kernels (stderr)
@@ -1409,8 +1412,8 @@ static int32_t run_epoch_device(psgd_ctx* ctx, const psgd_params* params, const 
             // {chain, helper} x {total, waiting}
             // chain_split: {total, row + dot + reduce, exchange wait, multiplier + update} per
             // compute wave
-            const bool split = ctx->last_variant >= 800;
-            const int KS = split ? 16 : ctx->last_variant >= 600 ? 6 : 4;
+            const bool split = plan.family == psgd::kFamSplit;
+            const int KS = split ? 16 : plan.family == psgd::kFamSparseLds ? 6 : 4;
             const int KST = split ? 16 : KS;   // stride per chain
             std::vector<unsigned long long> h((size_t)P * 16);
             HIP_TRY(hipMemcpyAsync(h.data(), L.stamps, h.size() * 8, hipMemcpyDeviceToHost, st));

@@ -530,7 +530,7 @@ __device__ __forceinline__ void wait_vmcnt_le(int k) {
 #undef PSGD_VMCNT_CASE
 }
 
-// Ring geometry chosen by the launcher (psgd_kernels.hip, launch_reg).
+// Ring geometry chosen on the host (plan_ring below; plan_chains, psgd_kernels.hip).
 struct RingGeom {
     int rows;         // R row slots
     int meta_blocks;  // MB meta blocks (16 rows each)
@@ -610,7 +610,12 @@ RingPlan dense_ring_plan(int nv, size_t budget);
 RingPlan split_ring_plan(int nv, int compute, bool conv, size_t budget);
 RingPlan block_ring_plan(int nv, bool conv, size_t budget);
 RingPlan block64_ring_plan(int nv, bool conv, size_t budget);
-// {R, MB, D, GS} of a launch, for psgd_ctx_last_ring (ring: nullable)
+// The ring a ChainPlan carries (plan_chains took it from its family's *_ring_plan): what the
+// launchers hand to the kernel, and what psgd_ctx_last_ring reports.
+inline RingPlan ring_of_plan(const ChainPlan& p) {
+    return RingPlan{RingGeom{p.ring[0], p.ring[1], p.ring[2], p.ring[3]}, (size_t)p.lds_bytes};
+}
+// {R, MB, D, GS} into ring[4] (nullable)
 inline void note_ring(int* ring, const RingGeom& g) {
     if (!ring) return;
     ring[0] = g.rows;

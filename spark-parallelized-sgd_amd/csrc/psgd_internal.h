@@ -75,22 +75,93 @@ struct ChainLaunch {
 #define PSGD_STAMP(...)
 #endif
 
-// Host-side launchers implemented in psgd_kernels.hip. Return hipError_t as int.
+// Host-side launchers. Return hipError_t as int.
 // storage: 0 = f64, 1 = f32; compute: 0 = f64, 1 = f32.
-// Kernel variants (*kernel_variant, psgd_ctx_last_kernel): 100 + NV chain_dense, 200 + LAYOUT
+// Kernel variants (ChainPlan::variant, psgd_ctx_last_kernel): 100 + NV chain_dense, 200 + LAYOUT
 // chain_general, 300 + NV chain_block, 400 + storage chain_sparse, 410 + storage chain_sparse_spec,
 // 420 + storage chain_sparse64, 500 + LAYOUT chain_multinomial, 600 + 10 (SK 8) + 20 (fp64) + storage chain_sparse_lds,
-// 700 + 10 (H - 1) + NV chain_block64, 800 + 10 H + NV chain_split.
-// *weights_in (nullable): where the launch left each chain's weights -- kWeightsOut: L.w_out
-// (launch_fold); kWeightsF32: L.wf32 as floats, w = walpha v (the fp32 CSR kernels,
-// launch_fold_f32); kWeightsF64: L.wf32 as doubles, w = walpha v (chain_sparse64, launch_fold_f64).
-int launch_chains(const ChainLaunch& L, const KParams& kp, int layout, int storage, int compute,
-                  int gradient, int updater, bool check_conv, int64_t min_ld, int64_t max_ld,
-                  int lds_spread, hipStream_t stream, int* kernel_variant, int64_t max_nnz = 0,
-                  int* weights_in = nullptr, int* ring = nullptr);
-// *ring (nullable, 4 ints): {R, MB, D, GS} of the LDS ring the launch gave chain_dense /
-// chain_split / chain_block / chain_block64; zeros when another kernel ran.
-// The same geometry without a launch (host only; the tests call it through its mangled name):
+// 700 + 10 (H - 1) + NV chain_block64, 800 + 10 H + NV chain_split; + 40 for the instances with the
+// per-sample break (tol > 0) of every family but chain_dense, chain_general, chain_multinomial
+// and chain_split.
+
+// ---- Which chain kernel runs an epoch, and what it needs ----
+// Everything the decision depends on. plan_chains is pure host code: no HIP call, no allocation.
+struct ChainSpec {
+    int32_t layout, storage, compute, gradient, updater;
+    bool conv;             // tol > 0: the per-sample convergence test runs
+    int32_t d;
+    int32_t nc;            // KParams::nc
+    int64_t min_ld, max_ld;   // dense: the shortest / longest row pitch of the non-empty partitions
+    int64_t max_nnz;       // CSR: the longest row
+    int64_t n_max;         // the longest chain
+    bool alpha_ok;         // KParams::alpha_ok
+    int64_t lds_budget;    // per-workgroup LDS budget of the ring kernels (<= 0: their 64 KiB default)
+    // the fp64 CSR kernels' per-chain vectors do not fit in HBM: such epochs run chain_general
+    bool f64_vectors_unavailable;
+};
+enum ChainFamily {
+    kFamDense = 0, kFamGeneral, kFamBlock, kFamBlock64, kFamSplit, kFamSparse, kFamSparseSpec,
+    kFamSparse64, kFamSparseLds, kFamMultinomial
+};
+enum ChainAfter { kAfterNone = 0, kAfterMarginLoss = 1, kAfterLogisticLoss64 = 2 };
+enum ChainSetup { kSetupNone = 0, kSetupWf32 = 1, kSetupW64 = 2 };
+enum ChainWnsq0 { kWnsq0None = 0, kWnsq0Rounded = 1, kWnsq0Exact = 2 };   // of float(w_in) / of w_in
+enum ChainBuf { kBufNone = 0, kBufF32 = 1, kBufF64 = 2 };
+struct ChainPlan {
+    ChainSpec spec;        // what was asked (the launchers take storage, gradient, updater from it)
+    int32_t family;        // ChainFamily
+    int32_t variant;       // as psgd_ctx_last_kernel reports it (legend above)
+    int32_t nv;            // 1-KiB vectors a row pitch takes (dense rows; 0: CSR)
+    int32_t h;             // chain waves of chain_block64 / compute waves of chain_split (else 0)
+    bool full;             // every row holds every lane's every vector (dense rows)
+    bool conv;             // the instance with the per-sample break
+    int32_t sk;            // speculation depth of chain_sparse_lds / chain_sparse_spec (else 0)
+    int64_t lds_k;         // chain_sparse_lds: features [0, K) live in LDS
+    bool tail;             // chain_sparse_lds: K < d, the rest lives in the chain's vector
+    int64_t lds_bytes;     // dynamic LDS of the launch
+    int32_t ring[4];       // {R, MB, D, GS} (zeros for kernels without a ring)
+    int32_t weights_in;    // WeightsIn: where the launch leaves each chain's weights
+    int32_t after;         // ChainAfter: the pass after the chain
+    int32_t setup;         // ChainSetup: the epoch set-up before it
+    int32_t wnsq0;         // ChainWnsq0: *L.wnsq0 computed before it
+    // the buffers the epoch gets (ChainLaunch pointers that are non-null)
+    int32_t zbuf;          // ChainBuf: L.zbuf / L.zbuf64, n_max entries a chain
+    int32_t vec;           // ChainBuf: L.wf32 as per-chain float / double vectors
+    int64_t vec_stride;    // L.wstride, in floats
+    bool walpha;           // L.walpha
+    bool wnsq0_buf;        // L.wnsq0
+    int64_t reroll_head;   // the vectors' first words the chains never touch (placement re-roll)
+};
+ChainPlan plan_chains(const ChainSpec& spec);
+// Launches the planned kernel with its set-up and the pass after it (kp.n_chains <= 0: nothing).
+// A plan whose instance is not built: hipErrorInvalidValue.
+int launch_chains(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+// One entry per kernel file, for the families it holds.
+int launch_block(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+int launch_block64(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+int launch_split(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+// chain_sparse, chain_sparse_spec, chain_sparse64 (psgd_sparse.hip)
+int launch_sparse(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+int launch_sparse_lds(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+// fp64 compute, any updater, dense or CSR rows. L.w_out holds n_chains * nc * d doubles, L.state
+// 3 * nc * d per chain.
+int launch_multinomial(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+// The CSR kernels' epoch set-up (psgd_sparse.hip), after checking L's vectors against the plan:
+// plan.setup (every chain's vector = float(w_in) / w_in, written by the whole GPU), then plan.wnsq0.
+int launch_chain_setup(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream);
+// Per-family geometry the plan asks the kernel files for (host only).
+int split_waves(int nv);                      // chain_split: compute waves at nv row vectors
+int64_t sparse_lds_row_cap();                 // chain_sparse_lds: entries a row may hold
+// chain_sparse_lds at depth sk (4, 8): the LDS head K of d features (-1: not even the tail's tag
+// table fits) and the launch's LDS for it. compute: 0 = f64, 1 = f32.
+int64_t sparse_lds_head(int sk, int compute, int64_t d);
+int64_t sparse_lds_bytes(int sk, int compute, int64_t d, int64_t K);
+// chain_sparse_spec (depth 8): its LDS for d features, or -1 when rows of max_nnz entries or the
+// d features do not fit.
+int64_t sparse_spec_bytes(int64_t d, int64_t max_nnz);
+
+// {R, MB, D, GS} of the LDS ring of chain_dense / chain_split / chain_block / chain_block64
+// without a launch (host only; the tests call it through its mangled name):
 // family kRing*, nv row vectors (1, 2, 4, 8; chain_split from 2), compute 0 = f64 / 1 = f32
 // (chain_split only), conv = the tol > 0 instances, budget = the per-workgroup LDS budget in
 // bytes (<= 0: the launchers' 64 KiB default). out5 = {R, MB, D, GS, LDS bytes of the launch}.
@@ -98,20 +169,6 @@ int launch_chains(const ChainLaunch& L, const KParams& kp, int layout, int stora
 // minimum ring. Returns 0, or -1 for a family / nv that does not exist.
 enum { kRingDense = 0, kRingSplit = 1, kRingBlock = 2, kRingBlock64 = 3 };
 int ring_geometry(int family, int nv, int compute, bool conv, int64_t budget, int32_t* out5);
-// The blocked fp32 kernel (psgd_block.hip): dense rows, Simple/SquaredL2, no per-sample
-// convergence test. launch_block_chains returns -3 when it does not apply.
-bool block_path_applies(int layout, int compute, int updater, bool check_conv, int storage,
-                        int64_t max_ld);
-int launch_block_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                        int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                        hipStream_t stream, int* kernel_variant, int* ring = nullptr);
-// The blocked fp64 kernel (psgd_block64.hip): dense rows, Simple/SquaredL2, fp64 compute, no
-// per-sample convergence test (the parity mode's throughput kernel). -3 when it does not apply.
-bool block64_path_applies(int layout, int compute, int updater, bool check_conv, int storage,
-                          int64_t max_ld);
-int launch_block64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                          int updater, int64_t min_ld, int64_t max_ld, int lds_spread,
-                          hipStream_t stream, int* kernel_variant, int* ring = nullptr);
 // lossSum of fp64 Logistic chains from the per-row dots in L.zbuf64 (psgd_kernels.hip).
 int launch_logistic_loss64(const ChainLaunch& L, int n_chains, hipStream_t stream);
 // lossSum of fp32 Logistic chains from the per-row margins in L.zbuf (psgd_block.hip).
@@ -126,54 +183,23 @@ int launch_fold(const double* w, int64_t w_stride, const double* rv, const doubl
 int launch_fold_f32(const float* wf32, int64_t wstride, const double* walpha, const double* rv,
                     const double* loss, const double* cnt, int n, int d, double* out,
                     int* watchdog, hipStream_t stream, double* mirror = nullptr);
-int launch_sq_terms(const double* a, const double* b, int d, double* out2, hipStream_t stream);
-int launch_steps(double step, int64_t n, double* steps, hipStream_t stream);
-// The fp32 CSR kernel (psgd_sparse.hip): weights as fp32 vectors in HBM (L.wf32).
-bool sparse_path_applies(int layout, int compute, int updater, bool check_conv);
-int launch_sparse_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                         int updater, int64_t max_nnz, hipStream_t stream, int* kernel_variant);
-// *L.wnsq0 = ||w_in||^2 in f64 (round_f32: of float(w_in), the fp32 kernels' weights).
-int launch_wnsq0(const ChainLaunch& L, int d, bool round_f32, hipStream_t st);
-// The fp64 CSR chain with HBM-resident weights (psgd_sparse.hip, chain_sparse64): Simple, and
-// SquaredL2 when kp.alpha_ok; the chain's double vector lives in its slice of L.wf32 (>= 2 (d +
-// 1152) floats), its alpha in L.walpha; weights end there (w = walpha v, launch_fold_f64).
-bool sparse64_path_applies(int layout, int compute, int updater, bool check_conv, bool alpha_ok);
-// PSGD_PER_SAMPLE=1 (tests, A/B): launch_chains keeps the per-sample kernels
-bool per_sample_forced();
-int launch_sparse64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                           int updater, hipStream_t stream, int* kernel_variant);
 // The combiner over chain_sparse64's vectors: w_p = walpha[p] * v_p[i] (v_p doubles).
 int launch_fold_f64(const double* wv, int64_t wstride_d, const double* walpha, const double* rv,
                     const double* loss, const double* cnt, int n, int d, double* out,
                     int* watchdog, hipStream_t stream, double* mirror = nullptr);
-// The fp32 CSR kernel with LDS-resident weights (psgd_sparse_lds.hip): rows of <= 128 non-zeros,
-// features [0, K) in LDS and [K, d) in L.wf32; -3 when it does not apply.
-bool sparse_lds_applies(int64_t d, int64_t max_nnz, int64_t n_max);
-int64_t sparse_lds_head(int64_t d);
-int launch_sparse_lds_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                             int updater, int64_t max_nnz, hipStream_t stream, int* kernel_variant);
-// The same kernel in fp64 compute (the parity mode's CSR throughput kernel): Simple, and
-// SquaredL2 when kp.alpha_ok; the chain's f64 vector lives in its slice of L.wf32, which must be
-// >= 2 (d + 1152) floats; weights end in L.w_out. -3 when it does not apply.
-bool sparse_lds64_applies(int64_t d, int64_t max_nnz, int updater, bool check_conv, bool alpha_ok,
-                          int64_t n_max);
-int launch_sparse_lds64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                               int updater, int64_t max_nnz, hipStream_t stream, int* kernel_variant);
-// Longest row of a device-resident CSR partition (synchronises `st`).
+int launch_sq_terms(const double* a, const double* b, int d, double* out2, hipStream_t stream);
+int launch_steps(double step, int64_t n, double* steps, hipStream_t stream);
 // Placement probe of the CSR chains' weight vectors (psgd_probe.hip): n_vectors waves, each
 // `iters` random 4-byte read-modify-writes per lane over its vector's first d_words words.
 int launch_vector_probe(float* w, int64_t stride_words, int n_vectors, int d_words, int iters, unsigned seed,
                         hipStream_t st);
+// Longest row of a device-resident CSR partition (synchronises `st`).
 int csr_max_nnz(const int64_t* d_row_ptr, int64_t n, int64_t* out, hipStream_t st);
+
 // RDD.sample(false, fraction, seed) per partition (PSGD.scala:242): from the registered
 // descriptors `base`, the epoch's descriptors `out` (rows/y/n_rows of the sampled subsequence;
 // rows and labels in `rows`/`ys`, `stride` entries per chain). xs_state[c] is the chain's
 // XORShiftRandom state (hashSeed of its partition seed, computed by the host).
-// The multinomial LogisticGradient chain (psgd_multinomial.hip): fp64 compute, any updater,
-// dense or CSR rows. L.w_out holds n_chains * nc * d doubles, L.state 3 * nc * d per chain.
-int launch_multinomial_chains(const ChainLaunch& L, const KParams& kp, int layout, int storage, int updater,
-                              bool check_conv, hipStream_t stream, int* kernel_variant);
-
 int launch_sample(const ChainDesc* base, ChainDesc* out, const uint64_t* xs_state, double fraction,
                   int32_t* rows, double* ys, int64_t stride, int n_chains, hipStream_t stream);
 
@@ -328,3 +354,10 @@ int launch_gather_csr(const ChainDesc* descs, const SplitPart* tab, int n_parts,
                       int64_t max_nnz, int64_t* tile_sum, int num_cus, hipStream_t st);
 
 }  // namespace psgd
+
+// The plan without a device, for the tests (ctypes; not part of the public ABI): spec[15] =
+// {layout, storage, compute, gradient, updater, conv, d, nc, min_ld, max_ld, max_nnz, n_max,
+// alpha_ok, lds_budget, f64_vectors_unavailable}; plan[24] receives {family, variant, nv, h, full,
+// conv, sk, lds_k, tail, lds_bytes, R, MB, D, GS, weights_in, after, setup, wnsq0, zbuf, vec,
+// vec_stride, walpha, wnsq0_buf, reroll_head}. Returns 0, or -1 when an array is null or short.
+extern "C" int32_t psgd_plan_chains(const int64_t* spec, int32_t n_spec, int64_t* plan, int32_t n_plan);

@@ -21,10 +21,10 @@
 // reference to rounding, not bitwise.
 #include "psgd_device.h"
 
-#include <string.h>
-#include "psgd_split.h"
+#include "psgd_dispatch.h"
 
 #include <stdlib.h>
+#include <string.h>
 
 namespace psgd {
 
@@ -919,173 +919,281 @@ int ring_geometry(int family, int nv, int compute, bool conv, int64_t budget, in
     return 0;
 }
 
-template <typename S, typename T, int GRAD, int UPD, bool CONV, int NV>
-static int launch_reg(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st, int* ring) {
-    // Ring geometry from the per-workgroup LDS budget (`lds`: chosen by the host so that the
-    // chains spread evenly over the CUs); the consumer reads rows t and t+1, the loader keeps
-    // loader_depth rows in flight and drains before it blocks on a full ring.
-    const RingPlan plan = dense_ring_plan(NV, lds > 0 ? lds : (size_t)64 * 1024);
-    const RingGeom g = plan.g;
-    const size_t bytes = plan.bytes;
-    note_ring(ring, g);
-    if (full) {
-        auto k = chain_dense<S, T, GRAD, UPD, CONV, NV, true>;
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(128), bytes, st, L, kp, g);
-    } else {
-        auto k = chain_dense<S, T, GRAD, UPD, CONV, NV, false>;
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(128), bytes, st, L, kp, g);
-    }
-    if constexpr (GRAD == G_LOGISTIC && sizeof(T) == 8) {
-        if (!L.zbuf64) return (int)hipErrorInvalidValue;
-        hipLaunchKernelGGL(logistic_loss64_kernel, dim3(kp.n_chains), dim3(1024), 0, st, L);
-    }
-    return (int)hipGetLastError();
-}
-
 int launch_logistic_loss64(const ChainLaunch& L, int n_chains, hipStream_t st) {
     if (!L.zbuf64) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(logistic_loss64_kernel, dim3(n_chains), dim3(1024), 0, st, L);
     return (int)hipGetLastError();
 }
 
-template <typename S, typename T, int GRAD, int UPD, bool CONV>
-static int dispatch_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld,
-                       size_t lds, hipStream_t st, int* variant, int* ring) {
-    constexpr int VEC = 16 / sizeof(S);
-    int nv = 1;
-    while (nv * 64 * VEC < max_ld) nv *= 2;
-    // FULL: every lane's every vector is inside every row (no exec masking on the loads).
-    const bool full = min_ld >= (int64_t)nv * 64 * VEC;
-    if (variant) *variant = 100 + nv;
-    // fp64 AdaGrad / Adam hold at most 16 doubles per lane (dispatch_layout): no NV past that
-    constexpr int NVMAX = (sizeof(T) == 8 && UPD >= U_ADAGRAD) ? 16 / VEC : 8;
-    switch (nv) {
-    case 1: return launch_reg<S, T, GRAD, UPD, CONV, 1>(L, kp, full, lds, st, ring);
-    case 2: return launch_reg<S, T, GRAD, UPD, CONV, 2>(L, kp, full, lds, st, ring);
-    case 4: return launch_reg<S, T, GRAD, UPD, CONV, 4>(L, kp, full, lds, st, ring);
-    case 8:
-        if constexpr (NVMAX >= 8) return launch_reg<S, T, GRAD, UPD, CONV, 8>(L, kp, full, lds, st, ring);
-        return -1;
-    default: return -1;
+// ------------------------------------------------------------------------------------------
+// plan_chains: which kernel runs the epoch and what it needs, decided once, on the
+// host. The environment switches of the selection are read here and nowhere else: every call
+// reads them (the tests set them between epochs), but for PSGD_B64_WAVES and PSGD_SPLIT, which
+// are read once per process: by the first plan that reaches their clause, psgd_plan_chains
+// included, so a test that wants them sets them before the first plan of its process.
+// ------------------------------------------------------------------------------------------
+namespace {
+
+const char* env_or_empty(const char* name) {
+    const char* e = getenv(name);
+    return e ? e : "";
+}
+
+void plan_ring_of(ChainPlan& p, const RingPlan& r) {
+    note_ring(p.ring, r.g);
+    p.lds_bytes = (int64_t)r.bytes;
+}
+
+// chain_sparse_lds at the depth PSGD_SPARSE_SK asks for (`depth`), in the arithmetic of
+// spec.compute. Whether it applies is decided at `depth`; the per-sample break has instances at
+// SK = 4 only. PSGD_SPARSE_LDS_HEAD=k caps the LDS-resident head (tests of the tail at small d).
+bool plan_sparse_lds(ChainPlan& p, int depth) {
+    const ChainSpec& s = p.spec;
+    if (s.max_nnz > sparse_lds_row_cap() || s.n_max > (int64_t)INT32_MAX) return false;
+    if (sparse_lds_head(depth, s.compute, s.d) < 0) return false;
+    p.family = kFamSparseLds;
+    p.sk = depth == 8 && !s.conv ? 8 : 4;
+    p.lds_k = sparse_lds_head(p.sk, s.compute, s.d);
+    const char* e = env_or_empty("PSGD_SPARSE_LDS_HEAD");
+    if (*e) {
+        const int64_t cap = atoll(e) & ~int64_t(3);
+        if (cap >= 0 && cap < p.lds_k) p.lds_k = cap;
     }
+    p.tail = p.lds_k < s.d;
+    p.lds_bytes = sparse_lds_bytes(p.sk, s.compute, s.d, p.lds_k);
+    p.variant = 600 + (s.conv ? 40 : 0) + (p.sk == 8 ? 10 : 0) + (s.compute == 0 ? 20 : 0) + s.storage;
+    return true;
 }
 
-template <typename S, int LAYOUT, int GRAD, int UPD, bool CONV>
-static int launch_gen(const ChainLaunch& L, const KParams& kp, hipStream_t st, int* variant) {
-    if (variant) *variant = 200 + LAYOUT;
-    hipLaunchKernelGGL((chain_general<S, LAYOUT, GRAD, UPD, CONV>), dim3(kp.n_chains), dim3(64), 0,
-                       st, L, kp);
-    return (int)hipGetLastError();
-}
+}  // namespace
 
-template <typename S, int GRAD, int UPD, bool CONV>
-static int dispatch_layout(const ChainLaunch& L, const KParams& kp, int layout, int compute,
-                           int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    constexpr int VEC = 16 / sizeof(S);
-    if constexpr (UPD <= U_L1) {
-        if (layout == kDense && max_ld <= 8 * 64 * VEC) {
-            if (compute == 1) return dispatch_nv<S, float, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-            return dispatch_nv<S, double, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
+ChainPlan plan_chains(const ChainSpec& s) {
+    ChainPlan p{};
+    p.spec = s;
+    p.conv = s.conv;
+    p.weights_in = kWeightsOut;
+    const bool dense = s.layout == kDense, csr = !dense, f32c = s.compute == 1;
+    const bool logistic = s.gradient == G_LOGISTIC;
+    const bool simple_l2 = s.updater == U_SIMPLE || s.updater == U_SQUARED_L2;
+    const int vec = s.storage == 1 ? 4 : 2;
+    const size_t budget = s.lds_budget > 0 ? (size_t)s.lds_budget : (size_t)64 * 1024;
+    // the rows' margins (fp32) / dots (fp64) of a dense binary Logistic epoch: its loss is summed
+    // after the chain by the kernels that leave them there
+    if (dense && logistic) p.zbuf = f32c ? kBufF32 : s.nc == 0 ? kBufF64 : kBufNone;
+    if (s.nc > 0) {   // LogisticGradient(numClasses > 2)
+        p.family = kFamMultinomial;
+        p.variant = 500 + s.layout;
+        p.lds_bytes = 2 * (int64_t)s.nc * (int64_t)sizeof(double);
+        return p;
+    }
+    if (dense) {
+        p.nv = 1;
+        while ((int64_t)p.nv * 64 * vec < s.max_ld) p.nv *= 2;
+        // FULL: every lane's every vector is inside every row (no exec masking on the loads)
+        p.full = s.min_ld >= (int64_t)p.nv * 64 * vec;
+    }
+    // a chain's vector of the CSR throughput kernels: d floats / doubles, and 128 + 1024 the
+    // kernels' masked-off lanes load from / store to (256-byte aligned: the set-up stores 16-byte
+    // vectors). PSGD_SPARSE_SK=8: chain_sparse_lds speculates 8 rows deep (A/B measurements).
+    const int64_t vstride = ((int64_t)s.d + 128 + 1024 + 63) / 64 * 64;
+    const int depth = csr && atoi(env_or_empty("PSGD_SPARSE_SK")) == 8 ? 8 : 4;
+    auto want_vectors = [&](int buf) {
+        p.vec = buf;
+        p.vec_stride = buf == kBufF64 ? 2 * vstride : vstride;
+        p.walpha = p.wnsq0_buf = true;
+        // (the fp32 LDS head of chain_sparse_lds, below which the chains never touch the vector;
+        // the fp64 head is shorter: half of it is inside the fp64 tail)
+        const int64_t head = sparse_lds_head(depth, 1, s.d);
+        p.reroll_head = head > 0 ? head : 0;
+    };
+    // every fp32-compute CSR epoch gets its vectors, whichever kernel runs
+    if (csr && f32c) want_vectors(kBufF32);
+
+    // PSGD_PER_SAMPLE=1 keeps the per-sample kernels (A/B measurements, tests)
+    const char* ps = env_or_empty("PSGD_PER_SAMPLE");
+    const bool throughput = !(*ps && *ps != '0');
+    // PSGD_SPARSE_KERNEL = lds | spec | plain forces an fp32 CSR kernel (any other non-empty value
+    // is `plain`); hbm64 keeps fp64 CSR epochs off the LDS kernel (tests, A/B measurements)
+    const char* force = env_or_empty("PSGD_SPARSE_KERNEL");
+
+    // The 8-row Gram-block kernels: dense rows, Simple / SquaredL2, rows of up to 8 KiB, any tol
+    // (PSGD_B64_CONV=0 sends tol > 0 to the per-sample kernels instead: tests of chain_split's
+    // break path, A/B measurements)
+    if (throughput && dense && simple_l2 && s.max_ld <= 8 * 64 * vec &&
+        !(s.conv && env_or_empty("PSGD_B64_CONV")[0] == '0')) {
+        if (f32c) {
+            p.family = kFamBlock;
+            p.variant = 300 + (s.conv ? 40 : 0) + p.nv;
+            plan_ring_of(p, block_ring_plan(p.nv, s.conv, budget));
+            p.after = logistic ? kAfterMarginLoss : kAfterNone;
+            return p;
         }
-    } else {
-        // AdaGrad / Adam: weights and status in registers. fp32: up to 8 row vectors per lane;
-        // fp64 (the parity mode): up to 16 doubles per lane (weights, status and two row buffers
-        // are 5 x 16 doubles = 160 VGPRs), d <= 1,024; past that chain_general, status in HBM
-        if (layout == kDense && compute == 1 && max_ld <= 8 * 64 * VEC)
-            return dispatch_nv<S, float, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-        if (layout == kDense && compute == 0 && max_ld <= 16 * 64)
-            return dispatch_nv<S, double, GRAD, UPD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
+        // two chain waves from NV = 2 on; PSGD_B64_WAVES=1 keeps one where its share of a block
+        // fits the registers (NV <= 4; A/B measurements)
+        static const bool one_wave = atoi(env_or_empty("PSGD_B64_WAVES")) == 1;
+        p.family = kFamBlock64;
+        p.h = (p.nv >= 2 && !(one_wave && p.nv <= 4)) ? 2 : 1;
+        p.variant = 700 + (s.conv ? 40 : 0) + 10 * (p.h - 1) + p.nv;
+        plan_ring_of(p, block64_ring_plan(p.nv, s.conv, budget));
+        p.after = logistic ? kAfterLogisticLoss64 : kAfterNone;
+        return p;
     }
-    if (layout == kDense) return launch_gen<S, kDense, GRAD, UPD, CONV>(L, kp, st, variant);
-    return launch_gen<S, kCsr, GRAD, UPD, CONV>(L, kp, st, variant);
-}
-
-template <typename S, int GRAD, int UPD>
-static int dispatch_conv(const ChainLaunch& L, const KParams& kp, int layout, int compute,
-                         bool conv, int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    if (conv) return dispatch_layout<S, GRAD, UPD, true>(L, kp, layout, compute, min_ld, max_ld, lds, st, variant, ring);
-    return dispatch_layout<S, GRAD, UPD, false>(L, kp, layout, compute, min_ld, max_ld, lds, st, variant, ring);
-}
-
-template <typename S, int GRAD>
-static int dispatch_upd(const ChainLaunch& L, const KParams& kp, int layout, int compute, int upd,
-                        bool conv, int64_t min_ld, int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    switch (upd) {
-    case U_SIMPLE: return dispatch_conv<S, GRAD, U_SIMPLE>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
-    case U_SQUARED_L2: return dispatch_conv<S, GRAD, U_SQUARED_L2>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
-    case U_L1: return dispatch_conv<S, GRAD, U_L1>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
-    case U_ADAGRAD: return dispatch_conv<S, GRAD, U_ADAGRAD>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
-    case U_ADAM: return dispatch_conv<S, GRAD, U_ADAM>(L, kp, layout, compute, conv, min_ld, max_ld, lds, st, variant, ring);
-    default: return -1;
+    // The fp32 CSR kernels, weights as fp32 vectors w = walpha v: in LDS (rows of <= 128 non-zeros,
+    // d up to ~65k), else speculating from HBM (no per-sample break), else plain
+    if (throughput && csr && f32c && simple_l2) {
+        p.weights_in = kWeightsF32;
+        p.setup = kSetupWf32;
+        p.wnsq0 = s.updater == U_SQUARED_L2 || s.conv ? kWnsq0Rounded : kWnsq0None;
+        const bool no_lds = *force && strcmp(force, "lds") != 0;
+        const bool no_spec = *force && strcmp(force, "spec") != 0;
+        if (!no_lds && plan_sparse_lds(p, depth)) return p;
+        const int64_t spec_bytes = sparse_spec_bytes(s.d, s.max_nnz);
+        if (!no_spec && !s.conv && spec_bytes >= 0) {
+            p.family = kFamSparseSpec;
+            p.variant = 410 + s.storage;
+            p.sk = 8;
+            p.lds_bytes = spec_bytes;
+            return p;
+        }
+        p.family = kFamSparse;
+        p.variant = 400 + (s.conv ? 40 : 0) + s.storage;
+        return p;
     }
-}
-
-template <typename S>
-static int dispatch_grad(const ChainLaunch& L, const KParams& kp, int layout, int compute, int grad,
-                         int upd, bool conv, int64_t min_ld, int64_t max_ld, size_t lds,
-                         hipStream_t st, int* variant, int* ring) {
-    switch (grad) {
-    case G_LOGISTIC: return dispatch_upd<S, G_LOGISTIC>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant, ring);
-    case G_LEAST_SQUARES: return dispatch_upd<S, G_LEAST_SQUARES>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant, ring);
-    case G_HINGE: return dispatch_upd<S, G_HINGE>(L, kp, layout, compute, upd, conv, min_ld, max_ld, lds, st, variant, ring);
-    default: return -1;
+    // The fp64 CSR kernels: Simple, and SquaredL2 while alpha stays in range; the chain's f64
+    // vector in LDS with its tail in HBM (weights end in w_out), or beyond that kernel's range
+    // all of it in HBM (w = walpha v). Without the vectors the epoch runs chain_general.
+    if (throughput && csr && !f32c && !s.f64_vectors_unavailable &&
+        (s.updater == U_SIMPLE || (s.updater == U_SQUARED_L2 && s.alpha_ok))) {
+        want_vectors(kBufF64);
+        p.wnsq0 = s.conv ? kWnsq0Exact : kWnsq0None;   // ||w_in||^2 for the break's norm recurrence
+        if (strcmp(force, "hbm64") != 0 && plan_sparse_lds(p, depth)) return p;
+        p.family = kFamSparse64;
+        p.variant = 420 + (s.conv ? 40 : 0) + s.storage;
+        p.weights_in = kWeightsF64;
+        p.setup = kSetupW64;
+        return p;
     }
+    // The feature-split per-sample chain: dense rows of 2 .. 8 KiB; AdaGrad / Adam / L1 always,
+    // Simple / SquaredL2 with the per-sample break that the blocked kernels did not take.
+    // PSGD_SPLIT=0 keeps chain_dense (A/B measurements)
+    static const bool split_off = env_or_empty("PSGD_SPLIT")[0] == '0';
+    if (throughput && dense && (!simple_l2 || s.conv) && !split_off && p.nv >= 2 && p.nv <= 8) {
+        p.family = kFamSplit;
+        p.h = split_waves(p.nv);
+        p.variant = 800 + 10 * p.h + p.nv;
+        plan_ring_of(p, split_ring_plan(p.nv, s.compute, s.conv, budget));
+        p.after = !logistic ? kAfterNone : f32c ? kAfterMarginLoss : kAfterLogisticLoss64;
+        return p;
+    }
+    // chain_dense, weights (and AdaGrad / Adam status) in registers: up to 8 row vectors per lane;
+    // fp64 AdaGrad / Adam up to 16 doubles per lane (weights, status and two row buffers are 5 x
+    // 16 doubles = 160 VGPRs), d <= 1,024
+    const bool wide_state = s.updater >= U_ADAGRAD && !f32c;
+    if (dense && s.max_ld <= (wide_state ? 16 * 64 : 8 * 64 * vec)) {
+        p.family = kFamDense;
+        p.variant = 100 + p.nv;
+        plan_ring_of(p, dense_ring_plan(p.nv, budget));
+        p.after = logistic && !f32c ? kAfterLogisticLoss64 : kAfterNone;
+        return p;
+    }
+    // chain_general: any row, weights in w_out and status in HBM
+    p.family = kFamGeneral;
+    p.variant = 200 + s.layout;
+    p.nv = 0;
+    p.full = false;
+    return p;
 }
 
-// PSGD_PER_SAMPLE=1 keeps the per-sample kernels (A/B measurements, tests; read at every launch)
-bool per_sample_forced() {
-    const char* e = getenv("PSGD_PER_SAMPLE");
-    return e && *e && *e != '0';
+extern "C" int32_t psgd_plan_chains(const int64_t* spec, int32_t n_spec, int64_t* plan, int32_t n_plan) {
+    if (!spec || !plan || n_spec < 15 || n_plan < 24) return -1;
+    ChainSpec s{};
+    s.layout = (int32_t)spec[0];
+    s.storage = (int32_t)spec[1];
+    s.compute = (int32_t)spec[2];
+    s.gradient = (int32_t)spec[3];
+    s.updater = (int32_t)spec[4];
+    s.conv = spec[5] != 0;
+    s.d = (int32_t)spec[6];
+    s.nc = (int32_t)spec[7];
+    s.min_ld = spec[8];
+    s.max_ld = spec[9];
+    s.max_nnz = spec[10];
+    s.n_max = spec[11];
+    s.alpha_ok = spec[12] != 0;
+    s.lds_budget = spec[13];
+    s.f64_vectors_unavailable = spec[14] != 0;
+    const ChainPlan p = plan_chains(s);
+    const int64_t out[24] = {p.family, p.variant, p.nv, p.h, p.full, p.conv, p.sk, p.lds_k, p.tail,
+                             p.lds_bytes, p.ring[0], p.ring[1], p.ring[2], p.ring[3], p.weights_in,
+                             p.after, p.setup, p.wnsq0, p.zbuf, p.vec, p.vec_stride, p.walpha,
+                             p.wnsq0_buf, p.reroll_head};
+    for (int k = 0; k < 24; ++k) plan[k] = out[k];
+    return 0;
 }
 
-int launch_chains(const ChainLaunch& L, const KParams& kp, int layout, int storage, int compute,
-                  int gradient, int updater, bool check_conv, int64_t min_ld, int64_t max_ld,
-                  int lds_spread, hipStream_t stream, int* kernel_variant, int64_t max_nnz,
-                  int* weights_in, int* ring) {
-    if (weights_in) *weights_in = kWeightsOut;
-    note_ring(ring, RingGeom{0, 0, 0, 0});   // stays zero unless a ring kernel launches
+// ------------------------------------------------------------------------------------------
+// Launchers: the plan's fields to the template instance (psgd_dispatch.h; the lists are the
+// built instances).
+// ------------------------------------------------------------------------------------------
+// chain_dense and chain_general, this file's two families, share one nest.
+static int launch_per_sample(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    const ChainSpec& s = p.spec;
+    const bool dense = p.family == kFamDense;
+    if (dense && p.after == kAfterLogisticLoss64 && !L.zbuf64) return (int)hipErrorInvalidValue;
+    // chain_dense's ring, from the per-workgroup LDS budget (chosen by the host so that the chains
+    // spread evenly over the CUs); the consumer reads rows t and t+1, the loader keeps
+    // loader_depth rows in flight and drains before it blocks on a full ring.
+    const RingGeom g = ring_of_plan(p).g;
+    const size_t bytes = (size_t)p.lds_bytes;
+    const int rc = dispatch_int<1, 0>(s.storage, [&](auto sc) {
+    return dispatch_int<G_LOGISTIC, G_LEAST_SQUARES, G_HINGE>(s.gradient, [&](auto gc) {
+    return dispatch_int<U_SIMPLE, U_SQUARED_L2, U_L1, U_ADAGRAD, U_ADAM>(s.updater, [&](auto uc) {
+    return dispatch_bool(p.conv, [&](auto conv) {
+        using S = FloatOf<decltype(sc)::value>;
+        constexpr int GRAD = decltype(gc)::value, UPD = decltype(uc)::value;
+        constexpr bool CONV = decltype(conv)::value;
+        if (dense)
+            return dispatch_int<1, 0>(s.compute, [&](auto cc) {
+                using T = FloatOf<decltype(cc)::value>;
+                auto launch = [&](auto nv) {
+                    return dispatch_bool(p.full, [&](auto full) {
+                        auto k = chain_dense<S, T, GRAD, UPD, CONV, decltype(nv)::value, decltype(full)::value>;
+                        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+                        hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(128), bytes, st, L, kp, g);
+                        return (int)hipGetLastError();
+                    });
+                };
+                // fp64 AdaGrad / Adam hold at most 16 doubles per lane: no NV = 8 on f32 rows
+                if constexpr (sizeof(T) == 8 && UPD >= U_ADAGRAD && sizeof(S) == 4)
+                    return dispatch_int<1, 2, 4>(p.nv, launch);
+                else
+                    return dispatch_int<1, 2, 4, 8>(p.nv, launch);
+            });
+        return dispatch_int<kDense, kCsr>(s.layout, [&](auto layout) {
+            hipLaunchKernelGGL((chain_general<S, decltype(layout)::value, GRAD, UPD, CONV>), dim3(kp.n_chains),
+                               dim3(64), 0, st, L, kp);
+            return (int)hipGetLastError();
+        });
+    }); }); }); });
+    if (rc || !dense || p.after != kAfterLogisticLoss64) return rc;
+    return launch_logistic_loss64(L, kp.n_chains, st);
+}
+
+int launch_chains(const ChainLaunch& L, const KParams& kp, const ChainPlan& plan, hipStream_t stream) {
     if (kp.n_chains <= 0) return 0;
-    if (kp.nc > 0)   // LogisticGradient(numClasses > 2)
-        return launch_multinomial_chains(L, kp, layout, storage, updater, check_conv, stream, kernel_variant);
-    const bool per_sample = per_sample_forced();
-    if (!per_sample && block64_path_applies(layout, compute, updater, check_conv, storage, max_ld))
-        return launch_block64_chains(L, kp, storage, gradient, updater, min_ld, max_ld, lds_spread,
-                                     stream, kernel_variant, ring);
-    if (!per_sample && block_path_applies(layout, compute, updater, check_conv, storage, max_ld))
-        return launch_block_chains(L, kp, storage, gradient, updater, min_ld, max_ld, lds_spread,
-                                   stream, kernel_variant, ring);
-    if (!per_sample && sparse_path_applies(layout, compute, updater, check_conv)) {
-        if (weights_in) *weights_in = kWeightsF32;
-        const int e = launch_sparse_chains(L, kp, storage, gradient, updater, max_nnz, stream, kernel_variant);
-        if (e != -3) return e;
-        if (weights_in) *weights_in = kWeightsOut;   // tol > 0 past the LDS kernel's range
+    switch (plan.family) {
+    case kFamDense:
+    case kFamGeneral: return launch_per_sample(L, kp, plan, stream);
+    case kFamBlock: return launch_block(L, kp, plan, stream);
+    case kFamBlock64: return launch_block64(L, kp, plan, stream);
+    case kFamSplit: return launch_split(L, kp, plan, stream);
+    case kFamSparse:
+    case kFamSparseSpec:
+    case kFamSparse64: return launch_sparse(L, kp, plan, stream);
+    case kFamSparseLds: return launch_sparse_lds(L, kp, plan, stream);
+    case kFamMultinomial: return launch_multinomial(L, kp, plan, stream);
+    default: return (int)hipErrorInvalidValue;
     }
-    // PSGD_SPARSE_KERNEL=hbm64 keeps fp64 CSR epochs off the LDS kernel (tests, A/B measurements;
-    // read at every launch)
-    const char* force = getenv("PSGD_SPARSE_KERNEL");
-    const bool hbm64 = force && strcmp(force, "hbm64") == 0;
-    if (!per_sample && !hbm64 && layout == kCsr && compute == 0 &&
-        sparse_lds64_applies(kp.d, max_nnz, updater, check_conv, kp.alpha_ok != 0, kp.n_max) && L.wf32)
-        return launch_sparse_lds64_chains(L, kp, storage, gradient, updater, max_nnz, stream, kernel_variant);
-    // fp64 CSR beyond the LDS kernel's d (C5): the chain's weights as a double vector in HBM
-    if (!per_sample && sparse64_path_applies(layout, compute, updater, check_conv, kp.alpha_ok != 0) && L.wf32 &&
-        L.walpha) {
-        if (weights_in) *weights_in = kWeightsF64;
-        return launch_sparse64_chains(L, kp, storage, gradient, updater, stream, kernel_variant);
-    }
-    if (!per_sample && split_path_applies(layout, updater, check_conv, storage, max_ld)) {
-        const int e = launch_split_chains(L, kp, storage, compute, gradient, updater, min_ld, max_ld,
-                                          lds_spread, stream, kernel_variant, ring);
-        if (e != -3) return e;
-    }
-    const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
-    if (storage == 1)
-        return dispatch_grad<float>(L, kp, layout, compute, gradient, updater, check_conv, min_ld,
-                                    max_ld, lds, stream, kernel_variant, ring);
-    return dispatch_grad<double>(L, kp, layout, compute, gradient, updater, check_conv, min_ld,
-                                 max_ld, lds, stream, kernel_variant, ring);
 }
 
 int launch_fold(const double* w, int64_t w_stride, const double* rv, const double* loss,

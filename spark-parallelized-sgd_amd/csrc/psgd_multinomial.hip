@@ -21,6 +21,7 @@
 // with the gradient staged in a per-chain scratch G (zero outside the row, reset after use).
 // Per-chain status (L.state): [SA | SB | G], (K-1)*d doubles each.
 #include "psgd_device.h"
+#include "psgd_dispatch.h"
 
 namespace psgd {
 
@@ -253,39 +254,20 @@ __global__ __launch_bounds__(64) void chain_multinomial(ChainLaunch L, KParams k
     }
 }
 
-template <typename S, int LAYOUT, int UPD>
-static int mn_launch(const ChainLaunch& L, const KParams& kp, bool conv, hipStream_t st, int* variant) {
-    if (variant) *variant = 500 + LAYOUT;
-    const size_t lds = (size_t)2 * (size_t)kp.nc * sizeof(double);
-    if (conv)
-        hipLaunchKernelGGL((chain_multinomial<S, LAYOUT, UPD, true>), dim3(kp.n_chains), dim3(64), lds, st, L, kp);
-    else
-        hipLaunchKernelGGL((chain_multinomial<S, LAYOUT, UPD, false>), dim3(kp.n_chains), dim3(64), lds, st, L, kp);
-    return (int)hipGetLastError();
-}
-
-template <typename S, int LAYOUT>
-static int mn_upd(const ChainLaunch& L, const KParams& kp, int upd, bool conv, hipStream_t st, int* variant) {
-    switch (upd) {
-    case U_SIMPLE: return mn_launch<S, LAYOUT, U_SIMPLE>(L, kp, conv, st, variant);
-    case U_SQUARED_L2: return mn_launch<S, LAYOUT, U_SQUARED_L2>(L, kp, conv, st, variant);
-    case U_L1: return mn_launch<S, LAYOUT, U_L1>(L, kp, conv, st, variant);
-    case U_ADAGRAD: return mn_launch<S, LAYOUT, U_ADAGRAD>(L, kp, conv, st, variant);
-    case U_ADAM: return mn_launch<S, LAYOUT, U_ADAM>(L, kp, conv, st, variant);
-    default: return -1;
-    }
-}
-
-int launch_multinomial_chains(const ChainLaunch& L, const KParams& kp, int layout, int storage, int updater,
-                              bool check_conv, hipStream_t stream, int* kernel_variant) {
-    if (kp.n_chains <= 0) return 0;
+int launch_multinomial(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    const ChainSpec& s = p.spec;
     if (kp.nc < 2 || kp.nc > kMultinomialMaxBlocks || !L.state) return (int)hipErrorInvalidValue;
-    if (storage == 1) {
-        if (layout == kDense) return mn_upd<float, kDense>(L, kp, updater, check_conv, stream, kernel_variant);
-        return mn_upd<float, kCsr>(L, kp, updater, check_conv, stream, kernel_variant);
-    }
-    if (layout == kDense) return mn_upd<double, kDense>(L, kp, updater, check_conv, stream, kernel_variant);
-    return mn_upd<double, kCsr>(L, kp, updater, check_conv, stream, kernel_variant);
+    const size_t lds = (size_t)2 * (size_t)kp.nc * sizeof(double);   // the K - 1 margins and multipliers
+    if (p.lds_bytes != (int64_t)lds) return (int)hipErrorInvalidValue;
+    return dispatch_int<1, 0>(s.storage, [&](auto sc) {
+    return dispatch_int<kDense, kCsr>(s.layout, [&](auto layout) {
+    return dispatch_int<U_SIMPLE, U_SQUARED_L2, U_L1, U_ADAGRAD, U_ADAM>(s.updater, [&](auto uc) {
+    return dispatch_bool(p.conv, [&](auto conv) {
+        hipLaunchKernelGGL((chain_multinomial<FloatOf<decltype(sc)::value>, decltype(layout)::value, decltype(uc)::value,
+                                              decltype(conv)::value>),
+                           dim3(kp.n_chains), dim3(64), lds, st, L, kp);
+        return (int)hipGetLastError();
+    }); }); }); });
 }
 
 }  // namespace psgd

@@ -26,6 +26,7 @@
 // ||w||^2 recurrence from ||w_in||^2 (L.wnsq0), as chain_sparse_lds does (its header), and leaves
 // the walk after the first passing sample.
 #include "psgd_device.h"
+#include "psgd_dispatch.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -664,56 +665,12 @@ size_t spec_lds_bytes(int d) {
     return sizeof(SpecHeader) + SR * sizeof(SpecSlot) + (((size_t)d * 2 + 15) / 16) * 16;
 }
 
-// any tol: with the per-sample break (tol > 0) chain_sparse_lds or chain_sparse runs it
-bool sparse_path_applies(int layout, int compute, int updater, bool check_conv) {
-    (void)check_conv;
-    return layout == kCsr && compute == 1 && (updater == U_SIMPLE || updater == U_SQUARED_L2);
-}
-
-template <typename S, int GRAD>
-static int sparse_upd(const ChainLaunch& L, const KParams& kp, int upd, hipStream_t st) {
-    const bool conv = kp.tol > 0.0;   // the per-sample break: instances of their own
-    auto k = upd == U_SIMPLE ? (conv ? chain_sparse<S, GRAD, U_SIMPLE, true> : chain_sparse<S, GRAD, U_SIMPLE, false>)
-                             : (conv ? chain_sparse<S, GRAD, U_SQUARED_L2, true>
-                                     : chain_sparse<S, GRAD, U_SQUARED_L2, false>);
-    hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(64), 0, st, L, kp);
-    return (int)hipGetLastError();
-}
-
-template <typename S>
-static int sparse_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, hipStream_t st) {
-    switch (grad) {
-    case G_LOGISTIC: return sparse_upd<S, G_LOGISTIC>(L, kp, upd, st);
-    case G_LEAST_SQUARES: return sparse_upd<S, G_LEAST_SQUARES>(L, kp, upd, st);
-    case G_HINGE: return sparse_upd<S, G_HINGE>(L, kp, upd, st);
-    default: return -3;
-    }
-}
-
-template <typename S, int GRAD, int SK, int SR>
-static int spec_upd(const ChainLaunch& L, const KParams& kp, int upd, hipStream_t st) {
-    const size_t lds = spec_lds_bytes<SK, SR>(kp.d);
-    auto k = upd == U_SIMPLE ? chain_sparse_spec<S, GRAD, U_SIMPLE, SK, SR>
-                             : chain_sparse_spec<S, GRAD, U_SQUARED_L2, SK, SR>;
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(128), lds, st, L, kp);
-    return (int)hipGetLastError();
-}
-
-template <typename S, int SK, int SR>
-static int spec_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, hipStream_t st) {
-    switch (grad) {
-    case G_LOGISTIC: return spec_upd<S, G_LOGISTIC, SK, SR>(L, kp, upd, st);
-    case G_LEAST_SQUARES: return spec_upd<S, G_LEAST_SQUARES, SK, SR>(L, kp, upd, st);
-    case G_HINGE: return spec_upd<S, G_HINGE, SK, SR>(L, kp, upd, st);
-    default: return -3;
-    }
-}
-
-template <int SK, int SR>
-static int spec_launch(const ChainLaunch& L, const KParams& kp, int storage, int grad, int upd, hipStream_t st) {
-    if (storage == 1) return spec_grad<float, SK, SR>(L, kp, grad, upd, st);
-    return spec_grad<double, SK, SR>(L, kp, grad, upd, st);
+// chain_sparse_spec<.., 8, 32>: its LDS for d features; -1 when it does not apply (rows of more
+// than SCAP entries, or d past a CU's LDS)
+int64_t sparse_spec_bytes(int64_t d, int64_t max_nnz) {
+    if (max_nnz > SCAP || d > INT32_MAX) return -1;
+    const size_t bytes = spec_lds_bytes<8, 32>((int)d);
+    return bytes <= 160 * 1024 ? (int64_t)bytes : -1;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -761,23 +718,6 @@ __global__ __launch_bounds__(1024) void wnsq0_kernel(const double* __restrict__ 
     if (threadIdx.x == 0) *out = s[0];
 }
 
-int launch_wnsq0(const ChainLaunch& L, int d, bool round_f32, hipStream_t st) {
-    hipLaunchKernelGGL(wnsq0_kernel, dim3(1), dim3(1024), 0, st, L.w_in, d, L.wnsq0, round_f32);
-    return (int)hipGetLastError();
-}
-
-static int sparse_epoch_init(const ChainLaunch& L, const KParams& kp, int updater, hipStream_t st) {
-    const int bx = (kp.d + 1023) / 1024;
-    int by = (2048 + bx - 1) / bx;          // >= 2048 blocks in all
-    by = by < kp.n_chains ? by : kp.n_chains;
-    const int per = (kp.n_chains + by - 1) / by;
-    by = (kp.n_chains + per - 1) / per;
-    hipLaunchKernelGGL(wf32_init_kernel, dim3(bx, by), dim3(256), 0, st, L.wf32, L.wstride, L.w_in,
-                       kp.d, kp.n_chains, per);
-    if (updater == U_SQUARED_L2 || kp.tol > 0.0) return launch_wnsq0(L, kp.d, true, st);
-    return (int)hipGetLastError();
-}
-
 // Epoch set-up of the fp64 CSR chains: every chain's double vector = w_in (GPU-wide, as
 // wf32_init_kernel; C5: 34 GB in ~5 ms).
 __global__ __launch_bounds__(256) void w64_init_kernel(double* __restrict__ wv, int64_t wstride_d,
@@ -796,85 +736,73 @@ __global__ __launch_bounds__(256) void w64_init_kernel(double* __restrict__ wv, 
     }
 }
 
-bool sparse64_path_applies(int layout, int compute, int updater, bool check_conv, bool alpha_ok) {
-    (void)check_conv;   // any tol: the per-sample break is a CONV instance (kp.tol > 0)
-    return layout == kCsr && compute == 0 &&
-           (updater == U_SIMPLE || (updater == U_SQUARED_L2 && alpha_ok));
-}
-
-template <typename S, int GRAD>
-static int sparse64_upd(const ChainLaunch& L, const KParams& kp, int upd, hipStream_t st) {
-    const bool conv = kp.tol > 0.0;   // the per-sample break: instances of their own
-    auto k = upd == U_SIMPLE ? (conv ? chain_sparse64<S, GRAD, U_SIMPLE, true> : chain_sparse64<S, GRAD, U_SIMPLE, false>)
-                             : (conv ? chain_sparse64<S, GRAD, U_SQUARED_L2, true>
-                                     : chain_sparse64<S, GRAD, U_SQUARED_L2, false>);
-    hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(64), 0, st, L, kp);
+int launch_chain_setup(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    // the chain's vector: [d] + [128] + [1024] floats / doubles inside its slice of L.wf32
+    const int64_t words = p.vec == kBufF64 ? 2 : 1;
+    if (p.vec == kBufNone || !L.wf32 || L.wstride < words * ((int64_t)kp.d + 128 + 1024) || (L.wstride & 3) ||
+        !L.walpha || !L.wnsq0)
+        return (int)hipErrorInvalidValue;
+    if (p.setup != kSetupNone) {
+        const int per_block = p.setup == kSetupWf32 ? 1024 : 512;   // features: 256 threads x 4 / x 2
+        const int bx = (kp.d + per_block - 1) / per_block;
+        int by = (2048 + bx - 1) / bx;          // >= 2048 blocks in all
+        by = by < kp.n_chains ? by : kp.n_chains;
+        const int per = (kp.n_chains + by - 1) / by;
+        by = (kp.n_chains + per - 1) / per;
+        if (p.setup == kSetupWf32)
+            hipLaunchKernelGGL(wf32_init_kernel, dim3(bx, by), dim3(256), 0, st, L.wf32, L.wstride, L.w_in,
+                               kp.d, kp.n_chains, per);
+        else
+            hipLaunchKernelGGL(w64_init_kernel, dim3(bx, by), dim3(256), 0, st, reinterpret_cast<double*>(L.wf32),
+                               L.wstride / 2, L.w_in, kp.d, kp.n_chains, per);
+    }
+    if (p.wnsq0 != kWnsq0None)
+        hipLaunchKernelGGL(wnsq0_kernel, dim3(1), dim3(1024), 0, st, L.w_in, kp.d, L.wnsq0,
+                           p.wnsq0 == kWnsq0Rounded);
     return (int)hipGetLastError();
 }
 
-template <typename S>
-static int sparse64_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, hipStream_t st) {
-    switch (grad) {
-    case G_LOGISTIC: return sparse64_upd<S, G_LOGISTIC>(L, kp, upd, st);
-    case G_LEAST_SQUARES: return sparse64_upd<S, G_LEAST_SQUARES>(L, kp, upd, st);
-    case G_HINGE: return sparse64_upd<S, G_HINGE>(L, kp, upd, st);
-    default: return -3;
-    }
-}
-
-int launch_sparse64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                           int updater, hipStream_t stream, int* kernel_variant) {
-    if (kp.n_chains <= 0) return 0;
-    if (!sparse64_path_applies(kCsr, 0, updater, false, kp.alpha_ok != 0)) return -3;
-    // the chain's f64 vector: [d] + [128] + [1024] doubles inside its slice of L.wf32
-    if (!L.wf32 || L.wstride < 2 * ((int64_t)kp.d + 128 + 1024) || (L.wstride & 3) || !L.walpha)
-        return (int)hipErrorInvalidValue;
-    const int bx = (kp.d + 511) / 512;
-    int by = (2048 + bx - 1) / bx;
-    by = by < kp.n_chains ? by : kp.n_chains;
-    const int per = (kp.n_chains + by - 1) / by;
-    by = (kp.n_chains + per - 1) / per;
-    hipLaunchKernelGGL(w64_init_kernel, dim3(bx, by), dim3(256), 0, stream, reinterpret_cast<double*>(L.wf32),
-                       L.wstride / 2, L.w_in, kp.d, kp.n_chains, per);
-    if (kp.tol > 0.0) {
-        // ||w_in||^2 for the per-sample break's norm recurrence
-        if (!L.wnsq0) return (int)hipErrorInvalidValue;
-        const int e = launch_wnsq0(L, kp.d, false, stream);
-        if (e) return e;
-    }
-    // variant 420 + 40 (the per-sample break) + storage
-    if (kernel_variant) *kernel_variant = 420 + (kp.tol > 0.0 ? 40 : 0) + storage;
-    if (storage == 1) return sparse64_grad<float>(L, kp, gradient, updater, stream);
-    return sparse64_grad<double>(L, kp, gradient, updater, stream);
-}
-
-int launch_sparse_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                         int updater, int64_t max_nnz, hipStream_t stream, int* kernel_variant) {
-    if (kp.n_chains <= 0) return 0;
-    if (!L.wf32 || L.wstride < (int64_t)kp.d + 128 + 1024 || (L.wstride & 3) || !L.walpha || !L.wnsq0)
-        return (int)hipErrorInvalidValue;
-    int rc = sparse_epoch_init(L, kp, updater, stream);
+// The entry of this file's three families: the plan's fields to the instance. Simple / SquaredL2
+// only; chain_sparse_spec has no per-sample break (plan.conv), the other two have instances of it.
+int launch_sparse(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    const ChainSpec& s = p.spec;
+    const int rc = launch_chain_setup(L, kp, p, st);
     if (rc) return rc;
-    // PSGD_SPARSE_KERNEL = lds | spec | plain forces a variant (tests, A/B measurements; read at
-    // every launch); default: the first that applies in that order
-    const char* force = getenv("PSGD_SPARSE_KERNEL");
-    const bool any = !force || !*force;
-    const bool no_lds = !any && strcmp(force, "lds") != 0;
-    const bool no_spec = !any && strcmp(force, "spec") != 0;
-    // first choice: the chain's weights in LDS (psgd_sparse_lds.hip), for rows of <= 128
-    // non-zeros and d up to ~65k features
-    if (!no_lds) {
-        rc = launch_sparse_lds_chains(L, kp, storage, gradient, updater, max_nnz, stream, kernel_variant);
-        if (rc != -3) return rc;
+    // f(storage, gradient, updater) over this file's instances
+    auto instance = [&](auto&& f) {
+        return dispatch_int<1, 0>(s.storage, [&](auto sc) {
+        return dispatch_int<G_LOGISTIC, G_LEAST_SQUARES, G_HINGE>(s.gradient, [&](auto gc) {
+        return dispatch_int<U_SIMPLE, U_SQUARED_L2>(s.updater, [&](auto uc) { return f(sc, gc, uc); }); }); });
+    };
+    auto one_wave = [&](auto k) {
+        hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(64), 0, st, L, kp);
+        return (int)hipGetLastError();
+    };
+    switch (p.family) {
+    case kFamSparse64:
+        return instance([&](auto sc, auto gc, auto uc) {
+            return dispatch_bool(p.conv, [&](auto conv) {
+                return one_wave(chain_sparse64<FloatOf<decltype(sc)::value>, decltype(gc)::value, decltype(uc)::value,
+                                               decltype(conv)::value>);
+            });
+        });
+    case kFamSparseSpec:
+        if (p.conv || p.sk != 8) return (int)hipErrorInvalidValue;
+        return instance([&](auto sc, auto gc, auto uc) {
+            auto k = chain_sparse_spec<FloatOf<decltype(sc)::value>, decltype(gc)::value, decltype(uc)::value, 8, 32>;
+            (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+            hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(128), (size_t)p.lds_bytes, st, L, kp);
+            return (int)hipGetLastError();
+        });
+    case kFamSparse:
+        return instance([&](auto sc, auto gc, auto uc) {
+            return dispatch_bool(p.conv, [&](auto conv) {
+                return one_wave(chain_sparse<FloatOf<decltype(sc)::value>, decltype(gc)::value, decltype(uc)::value,
+                                             decltype(conv)::value>);
+            });
+        });
+    default: return (int)hipErrorInvalidValue;
     }
-    // chain_sparse_spec has no per-sample break; chain_sparse has (variant 440 + storage)
-    if (!no_spec && kp.tol <= 0.0 && max_nnz <= SCAP && spec_lds_bytes<8, 32>(kp.d) <= 160 * 1024) {
-        if (kernel_variant) *kernel_variant = 410 + storage;
-        return spec_launch<8, 32>(L, kp, storage, gradient, updater, stream);
-    }
-    if (kernel_variant) *kernel_variant = 400 + (kp.tol > 0.0 ? 40 : 0) + storage;
-    if (storage == 1) return sparse_grad<float>(L, kp, gradient, updater, stream);
-    return sparse_grad<double>(L, kp, gradient, updater, stream);
 }
 
 // Longest row of a CSR partition (registration of device-resident rows).

@@ -49,6 +49,7 @@
 // D < tol^2 max(N, 1). After the first passing sample the rest of its unrolled group runs with
 // c = 0 (no update, loss or count) and the chain ends.
 #include "psgd_device.h"
+#include "psgd_dispatch.h"
 
 #include <stdlib.h>
 
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(192) void chain_sparse_lds(ChainLaunch L, KParams k
     const int32_t n_pad = (n + GS - 1) / GS * GS;
     const int32_t n_fill = (n_pad + SK + 1 + 7) / 8 * 8;
     // [d] (tail used) + [128] the loader's dummy sources + [1024] the chain's dummy targets (in
-    // T: for doubles the chain's slice of L.wf32 is twice as long, launch_sparse_lds64_chains)
+    // T: for doubles the chain's slice of L.wf32 is twice as long, plan_chains)
     T* V = reinterpret_cast<T*>(L.wf32 + (int64_t)chain * L.wstride);
 
     for (int32_t i = threadIdx.x; i < NT; i += blockDim.x) tagpos[i] = 0xFFFF;
@@ -751,103 +752,50 @@ __global__ __launch_bounds__(192) void chain_sparse_lds(ChainLaunch L, KParams k
     }
 }
 
-// The dispatch over every instantiation (left out of single-kernel ISA probes, tools/isa_probe.sh).
+// The plan's geometry questions and the family's entry (left out of single-kernel ISA probes,
+// tools/isa_probe.sh).
 #ifndef PSGD_NO_DISPATCH
-template <typename S, typename T, int GRAD, int SK, bool CONV>
-static int lds_upd_c(const ChainLaunch& L, const KParams& kp, int upd, int K, size_t lds, hipStream_t st) {
-    auto k = K < kp.d ? (upd == U_SIMPLE ? chain_sparse_lds<S, T, GRAD, U_SIMPLE, SK, true, CONV>
-                                         : chain_sparse_lds<S, T, GRAD, U_SQUARED_L2, SK, true, CONV>)
-                      : (upd == U_SIMPLE ? chain_sparse_lds<S, T, GRAD, U_SIMPLE, SK, false, CONV>
-                                         : chain_sparse_lds<S, T, GRAD, U_SQUARED_L2, SK, false, CONV>);
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(192), lds, st, L, kp, K);
-    return (int)hipGetLastError();
+// The chain, loader and tagger waves keep row numbers in 32 bits (n): a partition of more than
+// INT32_MAX rows (>= 32 GiB of 16-byte CSR rows, which fits in HBM) takes another kernel; the plan
+// sees to that.
+int64_t sparse_lds_row_cap() { return LCAP; }
+
+int64_t sparse_lds_head(int sk, int compute, int64_t d) {
+    if (compute == 1) return sk == 8 ? lds_head<8, float>(d) : lds_head<4, float>(d);
+    return sk == 8 ? lds_head<8, double>(d) : lds_head<4, double>(d);
 }
 
-// the per-sample break (tol > 0) has instances at the default depth SK = 4 only
-template <typename S, typename T, int GRAD, int SK>
-static int lds_upd(const ChainLaunch& L, const KParams& kp, int upd, int K, size_t lds, hipStream_t st) {
-    if constexpr (SK == 4) {
-        if (kp.tol > 0.0) return lds_upd_c<S, T, GRAD, SK, true>(L, kp, upd, K, lds, st);
-    }
-    return lds_upd_c<S, T, GRAD, SK, false>(L, kp, upd, K, lds, st);
+int64_t sparse_lds_bytes(int sk, int compute, int64_t d, int64_t K) {
+    if (compute == 1) return sk == 8 ? lds_bytes<8, float>(d, K) : lds_bytes<4, float>(d, K);
+    return sk == 8 ? lds_bytes<8, double>(d, K) : lds_bytes<4, double>(d, K);
 }
 
-template <typename S, typename T, int SK>
-static int lds_grad(const ChainLaunch& L, const KParams& kp, int grad, int upd, int K, size_t lds, hipStream_t st) {
-    switch (grad) {
-    case G_LOGISTIC: return lds_upd<S, T, G_LOGISTIC, SK>(L, kp, upd, K, lds, st);
-    case G_LEAST_SQUARES: return lds_upd<S, T, G_LEAST_SQUARES, SK>(L, kp, upd, K, lds, st);
-    case G_HINGE: return lds_upd<S, T, G_HINGE, SK>(L, kp, upd, K, lds, st);
-    default: return -3;
-    }
-}
-
-// Variant 600 + 40 (the per-sample break, tol > 0) + 10 (SK == 8) + 20 (fp64 compute) + storage
-// (1: f32 rows).
-template <int SK, typename T>
-static int lds_launch(const ChainLaunch& L, const KParams& kp, int storage, int gradient, int updater,
-                      hipStream_t stream, int* kernel_variant) {
-    int64_t K = lds_head<SK, T>(kp.d);
-    if (K < 0) return -3;
-    // tests: PSGD_SPARSE_LDS_HEAD=k caps the LDS-resident head (exercises the tail at small d)
-    if (const char* e = getenv("PSGD_SPARSE_LDS_HEAD"))
-        if (*e) { const int64_t cap = atoll(e) & ~int64_t(3); if (cap >= 0 && cap < K) K = cap; }
-    const size_t lds = (size_t)lds_bytes<SK, T>(kp.d, K);
-    if (kernel_variant) *kernel_variant = 600 + (kp.tol > 0.0 ? 40 : 0) + (SK == 8 ? 10 : 0) + (sizeof(T) == 8 ? 20 : 0) + storage;
-    if (storage == 1) return lds_grad<float, T, SK>(L, kp, gradient, updater, (int)K, lds, stream);
-    return lds_grad<double, T, SK>(L, kp, gradient, updater, (int)K, lds, stream);
-}
-
-// Speculation depth: 4 rows by default (tail gathers are L2 hits once the tails fit L2);
-// PSGD_SPARSE_SK=8 for A/B measurements (read at every launch).
-static int lds_depth() {
-    const char* e = getenv("PSGD_SPARSE_SK");
-    return (e && atoi(e) == 8) ? 8 : 4;
-}
-
-// The chain, loader and tagger waves keep row numbers in 32 bits (psgd_sparse_lds.hip: n): a
-// partition of more than INT32_MAX rows (>= 32 GiB of 16-byte CSR rows, which fits in HBM) takes
-// chain_sparse / chain_general instead.
-bool sparse_lds_applies(int64_t d, int64_t max_nnz, int64_t n_max) {
-    if (max_nnz > LCAP || n_max > (int64_t)INT32_MAX) return false;
-    return (lds_depth() == 8 ? lds_head<8, float>(d) : lds_head<4, float>(d)) >= 0;
-}
-
-int64_t sparse_lds_head(int64_t d) { return lds_depth() == 8 ? lds_head<8, float>(d) : lds_head<4, float>(d); }
-
-int launch_sparse_lds_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                             int updater, int64_t max_nnz, hipStream_t stream, int* kernel_variant) {
-    if (kp.n_chains <= 0) return 0;
-    if (!sparse_lds_applies(kp.d, max_nnz, kp.n_max)) return -3;
-    if (!L.wf32 || L.wstride < (int64_t)kp.d + 128 + 1024) return (int)hipErrorInvalidValue;
-    if (kp.tol > 0.0 && !L.wnsq0) return (int)hipErrorInvalidValue;
-    if (lds_depth() == 8 && kp.tol <= 0.0) return lds_launch<8, float>(L, kp, storage, gradient, updater, stream, kernel_variant);
-    return lds_launch<4, float>(L, kp, storage, gradient, updater, stream, kernel_variant);
-}
-
-bool sparse_lds64_applies(int64_t d, int64_t max_nnz, int updater, bool check_conv, bool alpha_ok, int64_t n_max) {
-    (void)check_conv;   // any tol: the per-sample break is a CONV instance (kp.tol > 0)
-    if (max_nnz > LCAP || n_max > (int64_t)INT32_MAX) return false;
-    if (updater != U_SIMPLE && !(updater == U_SQUARED_L2 && alpha_ok)) return false;
-    return (lds_depth() == 8 ? lds_head<8, double>(d) : lds_head<4, double>(d)) >= 0;
-}
-
-int launch_sparse_lds64_chains(const ChainLaunch& L, const KParams& kp, int storage, int gradient,
-                               int updater, int64_t max_nnz, hipStream_t stream, int* kernel_variant) {
-    if (kp.n_chains <= 0) return 0;
-    if (!sparse_lds64_applies(kp.d, max_nnz, updater, false, kp.alpha_ok != 0, kp.n_max)) return -3;
-    // the chain's f64 vector: [d] + [128] + [1024] doubles inside its slice of L.wf32
-    if (!L.wf32 || L.wstride < 2 * ((int64_t)kp.d + 128 + 1024) || (L.wstride & 3) || !L.w_out)
-        return (int)hipErrorInvalidValue;
-    if (kp.tol > 0.0) {
-        // ||w_in||^2 for the per-sample break's norm recurrence
-        if (!L.wnsq0) return (int)hipErrorInvalidValue;
-        const int e = launch_wnsq0(L, kp.d, false, stream);
-        if (e) return e;
-    }
-    if (lds_depth() == 8 && kp.tol <= 0.0) return lds_launch<8, double>(L, kp, storage, gradient, updater, stream, kernel_variant);
-    return lds_launch<4, double>(L, kp, storage, gradient, updater, stream, kernel_variant);
+// The plan's fields to the instance. Simple / SquaredL2 only; depth SK 4 (default) or 8, the
+// per-sample break (plan.conv) at SK = 4 only. fp32 compute: the chain's weights start as
+// float(w_in) in L.wf32 and end there; fp64: they end in L.w_out.
+int launch_sparse_lds(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    const ChainSpec& s = p.spec;
+    if (p.lds_k < 0 || p.lds_k > kp.d || p.tail != (p.lds_k < kp.d) || !L.w_out) return (int)hipErrorInvalidValue;
+    const int rc = launch_chain_setup(L, kp, p, st);
+    if (rc) return rc;
+    return dispatch_int<1, 0>(s.compute, [&](auto cc) {
+    return dispatch_int<8, 4>(p.sk, [&](auto sk) {
+    return dispatch_int<1, 0>(s.storage, [&](auto sc) {
+    return dispatch_int<G_LOGISTIC, G_LEAST_SQUARES, G_HINGE>(s.gradient, [&](auto gc) {
+        auto launch = [&](auto conv) {
+            return dispatch_bool(p.tail, [&](auto tail) {
+            return dispatch_int<U_SIMPLE, U_SQUARED_L2>(s.updater, [&](auto uc) {
+                auto k = chain_sparse_lds<FloatOf<decltype(sc)::value>, FloatOf<decltype(cc)::value>, decltype(gc)::value,
+                                          decltype(uc)::value, decltype(sk)::value, decltype(tail)::value,
+                                          decltype(conv)::value>;
+                (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+                hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(192), (size_t)p.lds_bytes, st, L, kp, (int)p.lds_k);
+                return (int)hipGetLastError();
+            }); });
+        };
+        if constexpr (decltype(sk)::value == 4) return dispatch_bool(p.conv, launch);
+        else return p.conv ? (int)hipErrorInvalidValue : launch(std::false_type{});
+    }); }); }); });
 }
 
 #endif  // PSGD_NO_DISPATCH

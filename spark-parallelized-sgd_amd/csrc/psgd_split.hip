@@ -37,7 +37,7 @@
 // fp32 the hardware exp2 / reciprocal (as chain_block); the row losses (log1pExp) are summed
 // after the chain from the stored margins, off the sequential path.
 #include "psgd_device.h"
-#include "psgd_split.h"
+#include "psgd_dispatch.h"
 
 #include <stdlib.h>
 
@@ -661,23 +661,14 @@ __global__ __launch_bounds__(64 * (H + 1)) void chain_split(ChainLaunch L, KPara
 // Launcher (left out of single-kernel ISA probes, tools/isa_probe.sh).
 // ------------------------------------------------------------------------------------------
 #ifndef PSGD_NO_DISPATCH
-namespace {
-
-template <typename S>
-int split_nv(int64_t max_ld) {
-    constexpr int VEC = 16 / sizeof(S);
-    int nv = 1;
-    while (nv * 64 * VEC < max_ld) nv *= 2;
-    return nv;
-}
-
-}  // namespace
+// compute waves per chain at nv row vectors
+int split_waves(int nv) { return nv < PSGD_SPLIT_HMAX ? nv : PSGD_SPLIT_HMAX; }
 
 // chain_split's ring: the fixed area of H = min(NV, PSGD_SPLIT_HMAX) compute waves exchanging
 // sizeof(T) / 4 (x 3 with the per-sample break) words a sample, then the meta and row rings; at
 // least PUB + 2 = 6 rows.
 RingPlan split_ring_plan(int nv, int compute, bool conv, size_t budget) {
-    const int h = nv < PSGD_SPLIT_HMAX ? nv : PSGD_SPLIT_HMAX;
+    const int h = split_waves(nv);
     const int pc = (compute == 1 ? 1 : 2) * (conv ? 3 : 1);   // 32-bit words per wave and sample
     return plan_ring(budget, split_fixed_bytes_of(h, pc), nv, 0, 1, 6);
 }
@@ -685,16 +676,14 @@ RingPlan split_ring_plan(int nv, int compute, bool conv, size_t budget) {
 namespace {
 
 template <typename S, typename T, int GRAD, int UPD, bool CONV, int NV>
-int launch_split(const ChainLaunch& L, const KParams& kp, bool full, size_t lds, hipStream_t st, int* ring) {
+int launch_split(const ChainLaunch& L, const KParams& kp, bool full, const RingPlan& plan, hipStream_t st) {
     constexpr int H = NV < PSGD_SPLIT_HMAX ? NV : PSGD_SPLIT_HMAX;
-    const RingPlan plan = split_ring_plan(NV, sizeof(T) == 8 ? 0 : 1, CONV, lds > 0 ? lds : (size_t)64 * 1024);
     if constexpr (GRAD == G_LOGISTIC) {
         // the rows' margins / dots, summed into the loss after the chain
         if (sizeof(T) == 8 ? !L.zbuf64 : !L.zbuf) return (int)hipErrorInvalidValue;
     }
     const RingGeom g = plan.g;
     const size_t bytes = plan.bytes;
-    note_ring(ring, g);
     auto k = full ? chain_split<S, T, GRAD, UPD, CONV, NV, true, H> : chain_split<S, T, GRAD, UPD, CONV, NV, false, H>;
     (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     hipLaunchKernelGGL(k, dim3(kp.n_chains), dim3(64 * (H + 1)), bytes, st, L, kp, g);
@@ -707,84 +696,28 @@ int launch_split(const ChainLaunch& L, const KParams& kp, bool full, size_t lds,
     return (int)hipGetLastError();
 }
 
-template <typename S, typename T, int GRAD, int UPD, bool CONV>
-int split_dispatch_nv(const ChainLaunch& L, const KParams& kp, int64_t min_ld, int64_t max_ld, size_t lds,
-                      hipStream_t st, int* variant, int* ring) {
-    constexpr int VEC = 16 / sizeof(S);
-    const int nv = split_nv<S>(max_ld);
-    const bool full = min_ld >= (int64_t)nv * 64 * VEC;
-    if (variant) *variant = 800 + 10 * (nv < PSGD_SPLIT_HMAX ? nv : PSGD_SPLIT_HMAX) + nv;
-    switch (nv) {
-    case 2: return launch_split<S, T, GRAD, UPD, CONV, 2>(L, kp, full, lds, st, ring);
-    case 4: return launch_split<S, T, GRAD, UPD, CONV, 4>(L, kp, full, lds, st, ring);
-    case 8: return launch_split<S, T, GRAD, UPD, CONV, 8>(L, kp, full, lds, st, ring);
-    default: return -3;
-    }
-}
-
-template <typename S, typename T, int GRAD, bool CONV>
-int split_dispatch_conv(const ChainLaunch& L, const KParams& kp, int updater, int64_t min_ld, int64_t max_ld,
-                        size_t lds, hipStream_t st, int* variant, int* ring) {
-    switch (updater) {
-    case U_ADAGRAD: return split_dispatch_nv<S, T, GRAD, U_ADAGRAD, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    case U_ADAM: return split_dispatch_nv<S, T, GRAD, U_ADAM, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    case U_L1: return split_dispatch_nv<S, T, GRAD, U_L1, CONV>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    default: break;
-    }
-    if constexpr (CONV) {   // tol = 0 keeps the blocked kernels for these two
-        if (updater == U_SIMPLE) return split_dispatch_nv<S, T, GRAD, U_SIMPLE, true>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-        if (updater == U_SQUARED_L2) return split_dispatch_nv<S, T, GRAD, U_SQUARED_L2, true>(L, kp, min_ld, max_ld, lds, st, variant, ring);
-    }
-    return -3;
-}
-
-template <typename S, typename T, int GRAD>
-int split_dispatch_upd(const ChainLaunch& L, const KParams& kp, int updater, int64_t min_ld, int64_t max_ld,
-                       size_t lds, hipStream_t st, int* variant, int* ring) {
-    // the per-sample convergence test runs exactly when tol > 0 (psgd_capi.cpp: check_conv)
-    if (kp.tol > 0.0) return split_dispatch_conv<S, T, GRAD, true>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
-    return split_dispatch_conv<S, T, GRAD, false>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
-}
-
-template <typename S, typename T>
-int split_dispatch_grad(const ChainLaunch& L, const KParams& kp, int gradient, int updater, int64_t min_ld,
-                        int64_t max_ld, size_t lds, hipStream_t st, int* variant, int* ring) {
-    switch (gradient) {
-    case G_LOGISTIC: return split_dispatch_upd<S, T, G_LOGISTIC>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
-    case G_LEAST_SQUARES: return split_dispatch_upd<S, T, G_LEAST_SQUARES>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
-    case G_HINGE: return split_dispatch_upd<S, T, G_HINGE>(L, kp, updater, min_ld, max_ld, lds, st, variant, ring);
-    default: return -3;
-    }
-}
-
 }  // namespace
 
-bool split_path_applies(int layout, int updater, bool check_conv, int storage, int64_t max_ld) {
-    if (layout != kDense) return false;
-    // AdaGrad / Adam / L1 always; Simple / SquaredL2 with the per-sample convergence test (at
-    // tol = 0 the blocked kernels take them)
-    if (updater != U_ADAGRAD && updater != U_ADAM && updater != U_L1 && !check_conv) return false;
-    // PSGD_SPLIT=0 keeps chain_dense (A/B measurements)
-    static const bool off = [] {
-        const char* e = getenv("PSGD_SPLIT");
-        return e && *e == '0';
-    }();
-    if (off) return false;
-    const int nv = storage == 1 ? split_nv<float>(max_ld) : split_nv<double>(max_ld);
-    return nv >= 2 && nv <= 8;
-}
-
-int launch_split_chains(const ChainLaunch& L, const KParams& kp, int storage, int compute, int gradient,
-                        int updater, int64_t min_ld, int64_t max_ld, int lds_spread, hipStream_t st,
-                        int* variant, int* ring) {
-    if (!split_path_applies(kDense, updater, kp.tol > 0.0, storage, max_ld)) return -3;
-    const size_t lds = (size_t)(lds_spread > 0 ? lds_spread : 0);
-    if (storage == 1) {
-        if (compute == 1) return split_dispatch_grad<float, float>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
-        return split_dispatch_grad<float, double>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
-    }
-    if (compute == 1) return split_dispatch_grad<double, float>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
-    return split_dispatch_grad<double, double>(L, kp, gradient, updater, min_ld, max_ld, lds, st, variant, ring);
+// The family's entry: the plan's fields to the instance. AdaGrad / Adam / L1 with or without the
+// per-sample break (plan.conv), Simple / SquaredL2 only with it (tol = 0 keeps the blocked
+// kernels for these two); NV 2, 4, 8.
+int launch_split(const ChainLaunch& L, const KParams& kp, const ChainPlan& p, hipStream_t st) {
+    const ChainSpec& s = p.spec;
+    return dispatch_int<1, 0>(s.storage, [&](auto sc) {
+    return dispatch_int<1, 0>(s.compute, [&](auto cc) {
+    return dispatch_int<G_LOGISTIC, G_LEAST_SQUARES, G_HINGE>(s.gradient, [&](auto gc) {
+    return dispatch_bool(p.conv, [&](auto conv) {
+        auto launch = [&](auto uc) {
+            return dispatch_int<2, 4, 8>(p.nv, [&](auto nv) {
+                return launch_split<FloatOf<decltype(sc)::value>, FloatOf<decltype(cc)::value>, decltype(gc)::value,
+                                    decltype(uc)::value, decltype(conv)::value, decltype(nv)::value>(L, kp, p.full, ring_of_plan(p), st);
+            });
+        };
+        if constexpr (decltype(conv)::value)
+            return dispatch_int<U_ADAGRAD, U_ADAM, U_L1, U_SIMPLE, U_SQUARED_L2>(s.updater, launch);
+        else
+            return dispatch_int<U_ADAGRAD, U_ADAM, U_L1>(s.updater, launch);
+    }); }); }); });
 }
 
 #endif  // PSGD_NO_DISPATCH

@@ -46,30 +46,44 @@ def test_kernels_are_gfx950_code_objects(pkg):
     assert b"chain_dense" in data and b"chain_general" in data and b"fold_kernel" in data
 
 
-def test_kernel_selection_limits_on_the_host(pkg):
-    """The dispatch predicates are host code (no device needed). chain_sparse_lds (fp32 and fp64)
+def test_kernel_selection_limits_on_the_host(pkg, monkeypatch):
+    """The selection is host code (plan_chains; no device needed). chain_sparse_lds (fp32 and fp64)
     counts a chain's rows in 32 bits, so a partition of more than INT32_MAX rows must not select
     it (such partitions fit in HBM as 16-byte CSR rows); chain_sparse64 takes fp64 CSR
     with Simple, or SquaredL2 while alpha stays in range, with or without the per-sample break
     (variants 420/421, 460/461)."""
-    lib = ctypes.CDLL(pkg._native.LIB_PATH)
-    lds = lib._ZN4psgd18sparse_lds_appliesElll
-    lds.restype, lds.argtypes = ctypes.c_bool, [ctypes.c_int64] * 3
-    lds64 = lib._ZN4psgd20sparse_lds64_appliesEllibbl
-    lds64.restype = ctypes.c_bool
-    lds64.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_bool, ctypes.c_bool, ctypes.c_int64]
-    s64 = lib._ZN4psgd21sparse64_path_appliesEiiibb
-    s64.restype = ctypes.c_bool
-    s64.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_bool, ctypes.c_bool]
+    from test_chain_plan import ADAGRAD, CSR, DENSE, F32, F64, L1, L2, SIMPLE, SWITCHES, chain_plan
+    for name in SWITCHES:
+        monkeypatch.delenv(name, raising=False)
+
+    def plan(compute, updater=SIMPLE, tol=False, alpha_ok=True, layout=CSR, d=47236, nnz=94, n_max=1000, storage=F32):
+        p = chain_plan(pkg, layout=layout, storage=storage, compute=compute, updater=updater, tol=tol, d=d,
+                       max_ld=d, max_nnz=nnz, n_max=n_max, alpha_ok=alpha_ok)
+        return p["family"], p["variant"]
+
     big = 2**31 - 1
-    assert lds(47236, 94, big) and not lds(47236, 94, big + 1)
-    assert lds64(47236, 94, 0, False, True, big) and not lds64(47236, 94, 0, False, True, big + 1)
-    assert not lds(47236, 129, 100)              # rows of more than 128 entries
-    CSR, DENSE, F64, F32 = 1, 0, 0, 1
-    SIMPLE, L2, L1 = 0, 1, 2
-    assert s64(CSR, F64, SIMPLE, False, False) and s64(CSR, F64, L2, False, True)
-    assert not s64(CSR, F64, L2, False, False)   # alpha out of range: chain_general renormalises
-    assert s64(CSR, F64, SIMPLE, True, True)      # the per-sample break runs in chain_sparse64 too
-    assert lds64(47236, 94, 0, True, True, 1000)   # ... and in chain_sparse_lds
-    assert not s64(CSR, F32, SIMPLE, False, True) and not s64(DENSE, F64, SIMPLE, False, True)
-    assert not s64(CSR, F64, L1, False, True)
+    assert plan(F32, n_max=big) == ("sparse_lds", 601) and plan(F32, n_max=big + 1)[0] != "sparse_lds"
+    assert plan(F64, alpha_ok=True, n_max=big) == ("sparse_lds", 621)
+    assert plan(F64, alpha_ok=True, n_max=big + 1)[0] != "sparse_lds"
+    assert plan(F32, nnz=129, n_max=100)[0] != "sparse_lds"   # rows of more than 128 entries
+    assert plan(F64, tol=True) == ("sparse_lds", 661)          # the per-sample break runs in chain_sparse_lds
+    # chain_sparse64: where the LDS kernel cannot apply (d = 2^22), and where it is switched off
+    for kw in ({"d": 2**22}, {}):
+        monkeypatch.setenv("PSGD_SPARSE_KERNEL", "" if kw else "hbm64")
+        assert plan(F64, SIMPLE, alpha_ok=False, **kw) == ("sparse64", 421)
+        assert plan(F64, L2, alpha_ok=True, **kw) == ("sparse64", 421)
+        assert plan(F64, SIMPLE, alpha_ok=False, storage=F64, **kw) == ("sparse64", 420)
+        # alpha out of range: chain_general renormalises
+        assert plan(F64, L2, alpha_ok=False, **kw) == ("general", 201)
+        # ... and the per-sample break runs in chain_sparse64 too
+        assert plan(F64, SIMPLE, tol=True, **kw) == ("sparse64", 461)
+        assert plan(F64, L2, tol=True, **kw) == ("sparse64", 461)
+        assert plan(F64, L2, tol=True, alpha_ok=False, **kw) == ("general", 201)
+        # never for fp32 compute, dense rows or L1
+        for upd in (SIMPLE, L2, L1, ADAGRAD):
+            for tol in (False, True):
+                assert plan(F32, upd, tol=tol, **kw)[0] != "sparse64"
+                for compute in (F64, F32):
+                    assert plan(compute, upd, tol=tol, layout=DENSE, d=512)[0] != "sparse64"
+                    assert plan(compute, upd, tol=tol, layout=DENSE, d=4096)[0] != "sparse64"
+        assert plan(F64, L1, **kw) == ("general", 201) and plan(F64, L1, tol=True, **kw) == ("general", 201)

@@ -34,9 +34,9 @@ static int launch_c(const psgd::ChainLaunch& L, const psgd::KParams& kp, int gra
     const size_t lds = 160 * 1024 - 512;
 #define NVCASE(G, U)                                                                              \
     if (grad == G && upd == U) {                                                                  \
-        if (d == 256) return psgd::launch_block<float, G, U, 1, C>(L, kp, true, lds, 0);          \
-        if (d == 512) return psgd::launch_block<float, G, U, 2, C>(L, kp, true, lds, 0);          \
-        if (d == 1024) return psgd::launch_block<float, G, U, 4, C>(L, kp, true, lds, 0);         \
+        if (d == 256) return psgd::launch_block<float, G, U, 1, C>(L, kp, true, psgd::block_ring_plan(1, C, lds), 0);          \
+        if (d == 512) return psgd::launch_block<float, G, U, 2, C>(L, kp, true, psgd::block_ring_plan(2, C, lds), 0);          \
+        if (d == 1024) return psgd::launch_block<float, G, U, 4, C>(L, kp, true, psgd::block_ring_plan(4, C, lds), 0);         \
     }
     NVCASE(0, 0) NVCASE(1, 0) NVCASE(0, 1) NVCASE(1, 1)
 #undef NVCASE

@@ -45,10 +45,10 @@ static int launch_s(const psgd::ChainLaunch& L, const psgd::KParams& kp, int gra
     constexpr int VEC = 16 / sizeof(S);
 #define NVCASE(G, U)                                                                              \
     if (grad == G && upd == U) {                                                                  \
-        if constexpr (H == 1) if (d == 64 * VEC) return psgd::launch_block64<S, G, U, 1, 1, C>(L, kp, true, lds, 0); \
-        if (d == 128 * VEC) return psgd::launch_block64<S, G, U, 2, H, C>(L, kp, true, lds, 0);      \
-        if (d == 256 * VEC) return psgd::launch_block64<S, G, U, 4, H, C>(L, kp, true, lds, 0);      \
-        if constexpr (H == 2) if (d == 512 * VEC) return psgd::launch_block64<S, G, U, 8, 2, C>(L, kp, true, lds, 0); \
+        if constexpr (H == 1) if (d == 64 * VEC) return psgd::launch_block64<S, G, U, 1, 1, C>(L, kp, true, psgd::block64_ring_plan(1, C, lds), 0); \
+        if (d == 128 * VEC) return psgd::launch_block64<S, G, U, 2, H, C>(L, kp, true, psgd::block64_ring_plan(2, C, lds), 0);      \
+        if (d == 256 * VEC) return psgd::launch_block64<S, G, U, 4, H, C>(L, kp, true, psgd::block64_ring_plan(4, C, lds), 0);      \
+        if constexpr (H == 2) if (d == 512 * VEC) return psgd::launch_block64<S, G, U, 8, 2, C>(L, kp, true, psgd::block64_ring_plan(8, C, lds), 0); \
     }
     NVCASE(0, 0) NVCASE(1, 0) NVCASE(0, 1) NVCASE(1, 1)
 #undef NVCASE
