@@ -186,8 +186,9 @@ int32_t psgd_initial_regval(psgd_ctx* ctx, const psgd_params* params, int32_t d,
  *
  * psgd_evaluate: the loss of weights w over every registered row, gradient.compute(x, y, w)._2
  * summed (PSGD.scala:254 at constant w). The weights are d long (the partitions' number of
- * features): the multinomial LogisticGradient is not scored (there is no num_classes argument; a
- * host that holds (K - 1) * d weights must refuse the call itself, as the Python package does).
+ * features): the multinomial LogisticGradient is not scored here (there is no num_classes argument; a
+ * host that holds (K - 1) * d weights must refuse the call itself, as the Python package does, and
+ * call psgd_evaluate_multinomial below).
  * out3 = {lossSum, (double)count, (double)nCorrect}: count is the number of registered rows,
  * nCorrect the rows with (x . w > 0.0 ? 1.0 : 0.0) == label for Logistic and Hinge (MLlib's default
  * thresholds, 0.5 on the sigmoid and 0.0 on the SVM margin) and 0 for LeastSquares.
@@ -212,6 +213,61 @@ int32_t psgd_evaluate_device(psgd_ctx* ctx, int32_t gradient, const double* d_w,
  * a partition that is not registered; an empty partition writes nothing. */
 int32_t psgd_predict(psgd_ctx* ctx, int64_t part, const double* w, double* margins);
 int32_t psgd_predict_device(psgd_ctx* ctx, int64_t part, const double* d_w, double* d_margins, void* stream);
+
+/* Scoring a multinomial logistic model (LogisticGradient with numClasses = K > 2; MLlib's users get
+ * it from LogisticRegressionModel.predict and MulticlassMetrics): w holds (K - 1) * d weights in
+ * K - 1 class blocks of d, W[c * d + i], class 0 the pivot. Per row, in fp64 whatever the storage:
+ *   margin_c  = sum_i x_i * W[c * d + i], c = 0 .. K - 2;
+ *   the class = predictPoint's: best = 0, max = 0.0; for c ascending, margin_c > max sets
+ *               best = c + 1 -- the pivot wins when no margin is positive, exact ties go to the
+ *               lowest class;
+ *   the loss  = LogisticGradient.compute(x, y, w)._2 for numClasses > 2 (the margins shifted by the
+ *               maximum when it is positive, exp(-max) in the maximum's place, label.toInt, marginY =
+ *               0 for label 0).
+ * psgd_evaluate_multinomial: out3 = {lossSum, (double)count, (double)nCorrect}, nCorrect the rows
+ * whose class equals the label; part_out (nullable) [n_parts * 2] = {lossSum_p, nCorrect_p}. Tiles,
+ * order of the sums, determinism, empty partitions and an all-empty registry: as psgd_evaluate.
+ * psgd_predict_multinomial: for registered partition `part`, classes[n_rows] (the class as a
+ * double, the labels' convention) and / or margins[n_rows * (K - 1)], row-major; either may be
+ * NULL, not both. An empty partition writes nothing.
+ * A row is read once; the class blocks live in LDS while they fit (dense rows), else they are read
+ * from L2 / HBM. Every K up to the training kernels' 4,097 classes is scored.
+ * Errors: PSGD_EINVAL for a null ctx / w / out3 (both outputs of a prediction) or num_classes < 3,
+ * PSGD_EUNSUPPORTED past 4,097 classes, PSGD_ESTATE when no partition is registered (a prediction:
+ * when `part` is not). Streams, registration waits and the epoch state: exactly as psgd_evaluate. */
+int32_t psgd_evaluate_multinomial(psgd_ctx* ctx, int32_t num_classes, const double* w, double* out3,
+                                  double* part_out);
+int32_t psgd_evaluate_multinomial_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w, double* d_out3,
+                                         double* d_part_out, void* stream);
+int32_t psgd_predict_multinomial(psgd_ctx* ctx, int64_t part, int32_t num_classes, const double* w, double* classes,
+                                 double* margins);
+int32_t psgd_predict_multinomial_device(psgd_ctx* ctx, int64_t part, int32_t num_classes, const double* d_w,
+                                        double* d_classes, double* d_margins, void* stream);
+
+/* The confusion table of n (prediction, label) pairs of doubles over K = num_classes classes:
+ * counts[label * K + prediction], K * K int64, rows actual, columns predicted. A pair with a value
+ * that is not a whole number in [0, K) is not counted: it adds one to *n_bad. Integer atomics only
+ * (a table per workgroup in LDS while K * K fits, flushed with 64-bit atomics): the same bits in any
+ * order. Both outputs are zeroed by the call; n = 0 leaves them zero. No partition need be
+ * registered; K >= 1 (a binary table is a table too).
+ * psgd_confusion_model: every registered row at weights w ((K - 1) * d, K >= 3): the classes come
+ * from the psgd_predict_multinomial kernels, written into scratch a partition at a time, the labels
+ * are the ones the registry holds on the device (nothing is copied).
+ * Errors: PSGD_EINVAL for a null ctx / counts / n_bad, n < 0, null predictions / labels (n > 0), a
+ * null w, num_classes < 1 (model form: < 3); PSGD_EUNSUPPORTED past 4,097 classes; the model form
+ * PSGD_ESTATE when no partition is registered. Streams and ordering as for the scoring calls. */
+int32_t psgd_confusion(psgd_ctx* ctx, const double* predictions, const double* labels, int64_t n,
+                       int32_t num_classes, int64_t* counts, int64_t* n_bad);
+int32_t psgd_confusion_device(psgd_ctx* ctx, const double* d_predictions, const double* d_labels, int64_t n,
+                              int32_t num_classes, int64_t* d_counts, int64_t* d_n_bad, void* stream);
+int32_t psgd_confusion_model(psgd_ctx* ctx, int32_t num_classes, const double* w, int64_t* counts, int64_t* n_bad);
+int32_t psgd_confusion_model_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w, int64_t* d_counts,
+                                    int64_t* d_n_bad, void* stream);
+
+/* The sizes at which the multiclass kernels change path, for tests and tools: out3 = {doubles of
+ * class blocks kept in LDS (at a pitch of d rounded up to whole 16-byte row vectors), the largest
+ * K - 1 whose softmax a single lane takes, the largest K * K of the confusion table kept in LDS}. */
+int32_t psgd_multiclass_switches(int32_t* out3);
 
 /* Column statistics over every registered row (MLlib 1.6.1 Statistics.colStats /
  * MultivariateOnlineSummarizer) -- what StandardScaler fits on before GeneralizedLinearAlgorithm

@@ -15,17 +15,17 @@ from .data import (CsrPartition, DensePartition, DeviceCsrPartition, DeviceParti
 from .gradient import Gradient, HingeGradient, LeastSquaresGradient, LogisticGradient
 from .feature import StandardScaler, StandardScalerModel, column_stats
 from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine, ParallelizedSGD, ShardedEngine,
-                           evaluate, make_params, runParallelizedSGD)
+                           evaluate, evaluate_multinomial, make_params, runParallelizedSGD)
 from .gradient_descent import GradientDescent, GradientSum, gradient_sum, runMiniBatchSGD
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
-from .evaluation import BinaryClassificationMetrics
+from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
 from .split import kFold, randomSplit
 from .util import loadLibSVMFile
 
 __all__ = [
-    "ParallelizedSGD", "runParallelizedSGD", "evaluate", "Evaluation", "HipEngine",
-    "BinaryClassificationMetrics", "randomSplit", "kFold",
+    "ParallelizedSGD", "runParallelizedSGD", "evaluate", "evaluate_multinomial", "Evaluation", "HipEngine",
+    "BinaryClassificationMetrics", "MulticlassMetrics", "randomSplit", "kFold",
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",

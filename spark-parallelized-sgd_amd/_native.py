@@ -34,6 +34,10 @@ EXPORTED = (
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
+    "psgd_evaluate_multinomial", "psgd_evaluate_multinomial_device",
+    "psgd_predict_multinomial", "psgd_predict_multinomial_device",
+    "psgd_confusion", "psgd_confusion_device", "psgd_confusion_model", "psgd_confusion_model_device",
+    "psgd_multiclass_switches",
     "psgd_cell_select", "psgd_cell_select_device", "psgd_gather_dense_device", "psgd_gather_csr_device",
 )
 
@@ -144,6 +148,15 @@ def lib():
             "psgd_binary_counts_model": ([vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_binary_counts_model_device": ([vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_metrics_sort_tile": ([], C.c_int32),
+            "psgd_evaluate_multinomial": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_evaluate_multinomial_device": ([vp, C.c_int32, vp, vp, vp, vp], C.c_int32),
+            "psgd_predict_multinomial": ([vp, C.c_int64, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_predict_multinomial_device": ([vp, C.c_int64, C.c_int32, vp, vp, vp, vp], C.c_int32),
+            "psgd_confusion": ([vp, vp, vp, C.c_int64, C.c_int32, vp, vp], C.c_int32),
+            "psgd_confusion_device": ([vp, vp, vp, C.c_int64, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_confusion_model": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_confusion_model_device": ([vp, C.c_int32, vp, vp, vp, vp], C.c_int32),
+            "psgd_multiclass_switches": ([i32p], C.c_int32),
             "psgd_cell_select": ([vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, vp, vp, vp], C.c_int32),
             "psgd_cell_select_device": ([vp, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, vp, vp, vp, vp],
                                         C.c_int32),
@@ -197,6 +210,15 @@ def sample_partition(seed: int, n: int, fraction: float, device: int = 0):
 def metrics_sort_tile() -> int:
     """The pairs one workgroup of the metrics kernels takes (psgd_metrics_sort_tile)."""
     return int(lib().psgd_metrics_sort_tile())
+
+
+def multiclass_switches() -> dict:
+    """The sizes at which the multiclass kernels change path (psgd_multiclass_switches): the doubles
+    of class blocks kept in LDS, the largest K - 1 whose softmax one lane takes, the largest K * K of
+    the confusion table kept in LDS."""
+    out = (C.c_int32 * 3)()
+    check(lib().psgd_multiclass_switches(out))
+    return {"lds_weights": int(out[0]), "lane_classes": int(out[1]), "confusion_lds_cells": int(out[2])}
 
 
 class _PinnedBuffer:
@@ -391,6 +413,68 @@ class Context:
 
     def predict_device(self, part: int, w_ptr, margins_ptr, stream=None):
         check(self._L.psgd_predict_device(self.handle, C.c_int64(part), w_ptr, margins_ptr, stream))
+
+    # scoring a multinomial logistic model ----------------------------------------------------------
+    def evaluate_multinomial(self, num_classes: int, w):
+        """Host-pointer form (psgd_evaluate_multinomial): (lossSum, count, nCorrect, partLoss,
+        partCorrect) of the (K - 1) d host weights w over every registered partition."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        nparts, _ = self.num_partitions()
+        out3 = np.zeros(3, dtype=np.float64)
+        part = np.zeros((max(nparts, 1), 2), dtype=np.float64)
+        check(self._L.psgd_evaluate_multinomial(self.handle, int(num_classes), w.ctypes.data, out3.ctypes.data,
+                                                part.ctypes.data))
+        return float(out3[0]), int(out3[1]), int(out3[2]), part[:nparts, 0].copy(), part[:nparts, 1].copy()
+
+    def evaluate_multinomial_device(self, num_classes: int, w_ptr, out3_ptr, part_ptr=None, stream=None):
+        check(self._L.psgd_evaluate_multinomial_device(self.handle, int(num_classes), w_ptr, out3_ptr, part_ptr,
+                                                       stream))
+
+    def predict_multinomial(self, part: int, n_rows: int, num_classes: int, w):
+        """Host-pointer form (psgd_predict_multinomial): (classes[n_rows], margins[n_rows, K - 1])."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        classes = np.zeros(int(n_rows), dtype=np.float64)
+        margins = np.zeros((int(n_rows), int(num_classes) - 1), dtype=np.float64)
+        check(self._L.psgd_predict_multinomial(self.handle, C.c_int64(part), int(num_classes), w.ctypes.data,
+                                               classes.ctypes.data, margins.ctypes.data))
+        return classes, margins
+
+    def predict_multinomial_device(self, part: int, num_classes: int, w_ptr, classes_ptr, margins_ptr=None,
+                                   stream=None):
+        check(self._L.psgd_predict_multinomial_device(self.handle, C.c_int64(part), int(num_classes), w_ptr,
+                                                      classes_ptr, margins_ptr, stream))
+
+    def confusion(self, predictions, labels, num_classes: int):
+        """Host-pointer form (psgd_confusion): (counts[K, K] int64, n_bad)."""
+        import numpy as np
+        predictions = np.ascontiguousarray(predictions, dtype=np.float64)
+        labels = np.ascontiguousarray(labels, dtype=np.float64)
+        K = int(num_classes)
+        counts = np.zeros((max(K, 1), max(K, 1)), dtype=np.int64)
+        bad = C.c_int64()
+        check(self._L.psgd_confusion(self.handle, predictions.ctypes.data, labels.ctypes.data,
+                                     C.c_int64(predictions.shape[0]), K, counts.ctypes.data, C.byref(bad)))
+        return counts, int(bad.value)
+
+    def confusion_device(self, predictions_ptr, labels_ptr, n: int, num_classes: int, counts_ptr, n_bad_ptr,
+                         stream=None):
+        check(self._L.psgd_confusion_device(self.handle, predictions_ptr, labels_ptr, C.c_int64(n), int(num_classes),
+                                            counts_ptr, n_bad_ptr, stream))
+
+    def confusion_model(self, num_classes: int, w):
+        """Host-pointer form (psgd_confusion_model): (counts[K, K] int64, n_bad) of every registered row."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        K = int(num_classes)
+        counts = np.zeros((max(K, 1), max(K, 1)), dtype=np.int64)
+        bad = C.c_int64()
+        check(self._L.psgd_confusion_model(self.handle, K, w.ctypes.data, counts.ctypes.data, C.byref(bad)))
+        return counts, int(bad.value)
+
+    def confusion_model_device(self, num_classes: int, w_ptr, counts_ptr, n_bad_ptr, stream=None):
+        check(self._L.psgd_confusion_model_device(self.handle, int(num_classes), w_ptr, counts_ptr, n_bad_ptr, stream))
 
     # column statistics and the column transform -------------------------------------------------
     def column_stats(self, d: int):

@@ -1729,6 +1729,284 @@ int32_t psgd_predict(psgd_ctx* ctx, int64_t part, const double* w, double* margi
     return PSGD_OK;
 }
 
+// ---- Scoring a multinomial logistic model (kernels in psgd_eval_mn.hip) ----
+// The same place in the context as psgd_evaluate / psgd_predict: score_prepare, the same tile and
+// partition scratch, no epoch state touched.
+
+static int32_t mn_classes(int32_t num_classes, int32_t least) {
+    if (num_classes < least)
+        return fail(PSGD_EINVAL, "num_classes must be >= " + std::to_string(least) + ", got " + std::to_string(num_classes));
+    if (num_classes - 1 > psgd::kMultinomialMaxBlocks)
+        return fail(PSGD_EUNSUPPORTED, "numClasses = " + std::to_string(num_classes) + " exceeds the built maximum of " +
+                                           std::to_string(psgd::kMultinomialMaxBlocks + 1) + " classes");
+    return PSGD_OK;
+}
+
+int32_t psgd_multiclass_switches(int32_t* out3) {
+    if (!out3) return fail(PSGD_EINVAL, "out3 is null");
+    out3[0] = psgd::kMnWLds;
+    out3[1] = psgd::kMnLaneClasses;
+    out3[2] = psgd::kConfLdsCells;
+    return PSGD_OK;
+}
+
+// score_enqueue for num_classes > 2: d_classes / d_margins (one partition only) instead of the sums.
+static int32_t score_enqueue_mn(psgd_ctx* ctx, int32_t num_classes, size_t p0, size_t n, const double* d_w,
+                                double* d_out3, double* d_part_out, double* d_classes, double* d_margins,
+                                hipStream_t st) {
+    const Part& first = ctx->parts.begin()->second;
+    const std::vector<psgd::EvalPart>& ep = ctx->eval_parts;
+    const int64_t n_items = ep[p0 + n].tile0 - ep[p0].tile0;
+    HIP_TRY(ctx->etiles.ensure((size_t)std::max<int64_t>(n_items, 1) * 2 * sizeof(double)));
+    HIP_TRY(ctx->epart.ensure(n * 2 * sizeof(double)));
+    double* tile_loss = ctx->etiles.as<double>();
+    double* tile_ok = tile_loss + std::max<int64_t>(n_items, 1);
+    const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>() + p0;
+    const psgd::EvalPart* d_ep = ctx->eparts.as<psgd::EvalPart>() + p0;
+    int e = psgd::launch_score_mn(descs, d_ep, (int)n, n_items, first.layout, first.dtype == PSGD_F32 ? 1 : 0, d_w,
+                                  first.d, num_classes, tile_loss, tile_ok, d_classes, d_margins, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("multinomial scoring kernel launch failed: ") + hipGetErrorString((hipError_t)e));
+    if (!d_out3) return PSGD_OK;
+    e = psgd::launch_eval_reduce(descs, d_ep, (int)n, tile_loss, tile_ok, ctx->epart.as<double>(), d_part_out,
+                                 d_out3, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("scoring reduction launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+// The host-pointer forms' staging of the (K - 1) d weights in ctx->ew, `extra` doubles after them
+// (takes ctx->mu; PSGD_ESTATE without partitions).
+static int32_t mn_stage_weights(psgd_ctx* ctx, int32_t num_classes, const double* w, size_t extra, double** d_w,
+                                double** d_extra) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const size_t D = (size_t)(num_classes - 1) * (size_t)ctx->parts.begin()->second.d;
+    DeviceGuard g(ctx->device);
+    // (the staging buffers are scratch too: a scoring call on another stream may still read them)
+    int32_t rc = scratch_acquire(ctx, ctx->stream);
+    if (rc) return rc;
+    HIP_TRY(ctx->ew.ensure((D + extra + 1) * sizeof(double)));
+    *d_w = ctx->ew.as<double>();
+    *d_extra = *d_w + D;
+    HIP_TRY(hipMemcpyAsync(*d_w, w, D * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    // the caller's array is pageable in general: the copy has left it when this returns
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_evaluate_multinomial_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w, double* d_out3,
+                                         double* d_part_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_w || !d_out3) return fail(PSGD_EINVAL, "d_w/d_out3 are null");
+    int32_t rc = mn_classes(num_classes, 3);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    return score_enqueue_mn(ctx, num_classes, 0, ctx->parts.size(), d_w, d_out3, d_part_out, nullptr, nullptr, st);
+}
+
+int32_t psgd_evaluate_multinomial(psgd_ctx* ctx, int32_t num_classes, const double* w, double* out3,
+                                  double* part_out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!w || !out3) return fail(PSGD_EINVAL, "w/out3 are null");
+    int32_t rc = mn_classes(num_classes, 3);
+    if (rc) return rc;
+    size_t P = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        P = ctx->parts.size();
+    }
+    double *d_w = nullptr, *d_out = nullptr;
+    rc = mn_stage_weights(ctx, num_classes, w, 3 + 2 * P, &d_w, &d_out);
+    if (rc) return rc;
+    rc = psgd_evaluate_multinomial_device(ctx, num_classes, d_w, d_out, d_out + 3, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    std::vector<double> h(3 + 2 * P);
+    HIP_TRY(hipMemcpyAsync(h.data(), d_out, h.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::memcpy(out3, h.data(), 3 * sizeof(double));
+    if (part_out) std::memcpy(part_out, h.data() + 3, 2 * P * sizeof(double));
+    return PSGD_OK;
+}
+
+int32_t psgd_predict_multinomial_device(psgd_ctx* ctx, int64_t part, int32_t num_classes, const double* d_w,
+                                        double* d_classes, double* d_margins, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_w) return fail(PSGD_EINVAL, "d_w is null");
+    int32_t rc = mn_classes(num_classes, 3);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const auto it = ctx->parts.find(part);
+    if (it == ctx->parts.end()) return fail(PSGD_ESTATE, "partition " + std::to_string(part) + " is not registered");
+    if (it->second.n_rows == 0) return PSGD_OK;
+    if (!d_classes && !d_margins) return fail(PSGD_EINVAL, "d_classes and d_margins are both null");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const size_t p0 = (size_t)std::distance(ctx->parts.begin(), it);
+    return score_enqueue_mn(ctx, num_classes, p0, 1, d_w, nullptr, nullptr, d_classes, d_margins, st);
+}
+
+int32_t psgd_predict_multinomial(psgd_ctx* ctx, int64_t part, int32_t num_classes, const double* w, double* classes,
+                                 double* margins) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!w) return fail(PSGD_EINVAL, "w is null");
+    int32_t rc = mn_classes(num_classes, 3);
+    if (rc) return rc;
+    size_t n = 0;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        const auto it = ctx->parts.find(part);
+        if (it == ctx->parts.end())
+            return fail(PSGD_ESTATE, "partition " + std::to_string(part) + " is not registered");
+        n = (size_t)it->second.n_rows;
+    }
+    if (n == 0) return PSGD_OK;
+    if (!classes && !margins) return fail(PSGD_EINVAL, "classes and margins are both null");
+    const size_t C1 = (size_t)num_classes - 1;
+    double *d_w = nullptr, *d_out = nullptr;
+    rc = mn_stage_weights(ctx, num_classes, w, n * (1 + C1), &d_w, &d_out);
+    if (rc) return rc;
+    rc = psgd_predict_multinomial_device(ctx, part, num_classes, d_w, classes ? d_out : nullptr,
+                                         margins ? d_out + n : nullptr, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    if (classes) HIP_TRY(hipMemcpyAsync(classes, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (margins)
+        HIP_TRY(hipMemcpyAsync(margins, d_out + n, n * C1 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+static int32_t confusion_launch_failed(int e) {
+    return fail(PSGD_EDEVICE, std::string("confusion kernel launch failed: ") + hipGetErrorString((hipError_t)e));
+}
+
+int32_t psgd_confusion_device(psgd_ctx* ctx, const double* d_predictions, const double* d_labels, int64_t n,
+                              int32_t num_classes, int64_t* d_counts, int64_t* d_n_bad, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (n < 0) return fail(PSGD_EINVAL, "n must be >= 0");
+    if (n > 0 && (!d_predictions || !d_labels)) return fail(PSGD_EINVAL, "predictions/labels are null");
+    if (!d_counts || !d_n_bad) return fail(PSGD_EINVAL, "counts/n_bad are null");
+    int32_t rc = mn_classes(num_classes, 1);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = scratch_acquire(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)num_classes * num_classes * sizeof(int64_t), st));
+    HIP_TRY(hipMemsetAsync(d_n_bad, 0, sizeof(int64_t), st));
+    const int e = psgd::launch_confusion(d_predictions, d_labels, n, num_classes, d_counts, d_n_bad, ctx->num_cus, st);
+    return e ? confusion_launch_failed(e) : PSGD_OK;
+}
+
+int32_t psgd_confusion_model_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w, int64_t* d_counts,
+                                    int64_t* d_n_bad, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_w) return fail(PSGD_EINVAL, "d_w is null");
+    if (!d_counts || !d_n_bad) return fail(PSGD_EINVAL, "counts/n_bad are null");
+    int32_t rc = mn_classes(num_classes, 3);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    int64_t longest = 0;
+    for (auto& kv : ctx->parts) longest = std::max(longest, kv.second.n_rows);
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)num_classes * num_classes * sizeof(int64_t), st));
+    HIP_TRY(hipMemsetAsync(d_n_bad, 0, sizeof(int64_t), st));
+    // a partition's classes go to scratch and are counted against the labels where the registry
+    // holds them; the next partition's classes reuse the scratch (stream order)
+    HIP_TRY(ctx->mscratch.ensure((size_t)std::max<int64_t>(longest, 1) * sizeof(double)));
+    double* classes = ctx->mscratch.as<double>();
+    size_t p = 0;
+    for (auto& kv : ctx->parts) {
+        const Part& q = kv.second;
+        if (q.n_rows > 0) {
+            rc = score_enqueue_mn(ctx, num_classes, p, 1, d_w, nullptr, nullptr, classes, nullptr, st);
+            if (rc) return rc;
+            const int e = psgd::launch_confusion(classes, q.y, q.n_rows, num_classes, d_counts, d_n_bad, ctx->num_cus, st);
+            if (e) return confusion_launch_failed(e);
+        }
+        ++p;
+    }
+    return PSGD_OK;
+}
+
+// The host-pointer forms' way back: {n_bad, counts[K * K]} at d_out.
+static int32_t confusion_read_back(psgd_ctx* ctx, const int64_t* d_out, int32_t num_classes, int64_t* counts,
+                                   int64_t* n_bad) {
+    DeviceGuard g(ctx->device);
+    const size_t cells = (size_t)num_classes * num_classes;
+    HIP_TRY(hipMemcpyAsync(n_bad, d_out, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(counts, d_out + 1, cells * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_confusion(psgd_ctx* ctx, const double* predictions, const double* labels, int64_t n,
+                       int32_t num_classes, int64_t* counts, int64_t* n_bad) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (n < 0) return fail(PSGD_EINVAL, "n must be >= 0");
+    if (n > 0 && (!predictions || !labels)) return fail(PSGD_EINVAL, "predictions/labels are null");
+    if (!counts || !n_bad) return fail(PSGD_EINVAL, "counts/n_bad are null");
+    int32_t rc = mn_classes(num_classes, 1);
+    if (rc) return rc;
+    const size_t N = (size_t)n, cells = (size_t)num_classes * num_classes;
+    int64_t* base = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        // {n_bad, counts[K * K], predictions[n], labels[n]}
+        HIP_TRY(ctx->mio.ensure((1 + cells + 2 * N + 1) * 8));
+        base = ctx->mio.as<int64_t>();
+        if (N) {
+            HIP_TRY(hipMemcpyAsync(base + 1 + cells, predictions, N * 8, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(base + 1 + cells + N, labels, N * 8, hipMemcpyHostToDevice, ctx->stream));
+            // the caller's arrays are pageable in general: the copies have left them when this returns
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+    }
+    rc = psgd_confusion_device(ctx, reinterpret_cast<double*>(base + 1 + cells),
+                               reinterpret_cast<double*>(base + 1 + cells + N), n, num_classes, base + 1, base,
+                               ctx->stream);
+    if (rc) return rc;
+    return confusion_read_back(ctx, base, num_classes, counts, n_bad);
+}
+
+int32_t psgd_confusion_model(psgd_ctx* ctx, int32_t num_classes, const double* w, int64_t* counts, int64_t* n_bad) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!w) return fail(PSGD_EINVAL, "w is null");
+    if (!counts || !n_bad) return fail(PSGD_EINVAL, "counts/n_bad are null");
+    int32_t rc = mn_classes(num_classes, 3);
+    if (rc) return rc;
+    const size_t cells = (size_t)num_classes * num_classes;
+    double *d_w = nullptr, *d_out = nullptr;
+    rc = mn_stage_weights(ctx, num_classes, w, 1 + cells, &d_w, &d_out);
+    if (rc) return rc;
+    int64_t* out = reinterpret_cast<int64_t*>(d_out);
+    rc = psgd_confusion_model_device(ctx, num_classes, d_w, out + 1, out, ctx->stream);
+    if (rc) return rc;
+    return confusion_read_back(ctx, out, num_classes, counts, n_bad);
+}
+
 // ---- Binary classification metrics (kernels in psgd_metrics.hip) ----
 // The same place in the context as the scoring calls: scratch of their own (ctx->mscratch, and
 // ctx->mio for the host-pointer forms' staging), no epoch state touched. The array forms read no

@@ -10,6 +10,7 @@
 // partition-index order (the combiner's order, PSGD.scala:271-276). No floating-point atomics:
 // a partition's sum is the same bits whatever the grid size and whatever else is registered.
 #include "psgd_device.h"
+#include "psgd_eval.h"
 
 namespace psgd {
 namespace {
@@ -20,30 +21,6 @@ constexpr int kEvalRows = 4;          // dense: rows a lane group keeps in fligh
 constexpr int kEvalWLds = 4096;       // dense: weights of up to this many features live in LDS
                                       // (32 KiB beside the waves' 8 KiB of dots: three workgroups a CU)
 constexpr int kReduceBlock = 1024;
-
-// Sum over aligned groups of gl (a power of two, wave-uniform) lanes: the first log2(gl) steps of
-// wave_sum. Every lane of a group ends with the same bits.
-__device__ __forceinline__ double group_sum(double v, int gl) {
-    if (gl > 1) v = v + dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-    if (gl > 2) v = v + dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-    if (gl > 4) v = v + dpp_mov<0x141>(v);   // row_half_mirror
-    if (gl > 8) v = v + dpp_mov<0x140>(v);   // row_mirror
-    if (gl > 16) v = swap_sum16(v);
-    if (gl > 32) v = swap_sum32(v);
-    return v;
-}
-
-// The item's partition: the last p with first tile <= item (empty partitions share their first
-// tile with the next one, so the last such p is the one that owns the tile). Wave-uniform.
-__device__ __forceinline__ int item_partition(const EvalPart* ep, int P, int64_t item) {
-    const int64_t base = ep[0].tile0;
-    int lo = 0, hi = P;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (ep[mid].tile0 - base <= item) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // Loss and MLlib's default-threshold prediction of one row from its dot (LogisticRegressionModel:
 // sigmoid > 0.5, SVMModel: margin > 0.0 -- both dot > 0.0).
@@ -61,11 +38,6 @@ __device__ __forceinline__ void score_row(double dot, double y, double& loss, do
 // i of the buffer in lane i % 64 -- labels read and margins written coalesced. Lane l adds its rows
 // l, l + 64, ... in order: fixed by the tile's geometry like everything else.
 constexpr int kDotBuf = 256;
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 template <int GRAD>
 __device__ __forceinline__ void score_buffer(const double* buf, int n, const double* __restrict__ y,
                                              int64_t row0, double* __restrict__ margins, int lane,

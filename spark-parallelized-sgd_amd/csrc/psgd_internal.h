@@ -227,6 +227,28 @@ int launch_score(const ChainDesc* descs, const EvalPart* ep, int n_parts, int64_
 int launch_eval_reduce(const ChainDesc* descs, const EvalPart* ep, int n_parts, const double* tile_loss,
                        const double* tile_ok, double* part, double* part_out, double* out3, hipStream_t st);
 
+// ---- Scoring a multinomial logistic model at fixed weights (psgd_eval_mn.hip) ----
+// The path switches: the class blocks live in LDS as f64 while (K - 1) * mn_lds_pitch(d) <= kMnWLds
+// doubles (dense rows; CSR rows gather them from L2 / HBM); a lane scores a whole row's softmax while
+// K - 1 <= kMnLaneClasses, past it the wave takes a row at a time with its lanes across the classes;
+// confusion_count keeps a K x K table per workgroup in LDS while K * K <= kConfLdsCells.
+constexpr int kMnWLds = 6144;
+constexpr int kMnLaneClasses = 64;
+constexpr int kConfLdsCells = 4096;
+// A class block's pitch in LDS: d rounded up to whole 16-byte vectors of the storage dtype.
+int64_t mn_lds_pitch(int d, int storage);
+// As launch_score for num_classes = K > 2 at weights w[(K - 1) * d]: tile_loss / tile_ok [n_items]
+// receive each tile's loss sum and correct predictions (predicted class == label); classes
+// (nullable) [n_rows] every row's predicted class as a double and margins (nullable) [n_rows * (K - 1)]
+// its raw margins, row-major -- both for one partition only.
+int launch_score_mn(const ChainDesc* descs, const EvalPart* ep, int n_parts, int64_t n_items, int layout, int storage,
+                    const double* w, int d, int num_classes, double* tile_loss, double* tile_ok, double* classes,
+                    double* margins, int num_cus, hipStream_t st);
+// counts[label * K + prediction] += 1 for each of the n pairs whose two values are whole numbers in
+// [0, K); every other pair adds 1 to *n_bad. Integer atomics: exact in any order. The caller zeroes both.
+int launch_confusion(const double* pred, const double* lab, int64_t n, int num_classes, int64_t* counts,
+                     int64_t* n_bad, int num_cus, hipStream_t st);
+
 // ---- Column statistics and the column transform (psgd_colstats.hip) ----
 // The tiling of these passes: the same for every partition of a registry (one d, one storage).
 // tile0[p] (device, [n_parts + 1]) is partition p's first tile, the tiles numbered across the

@@ -1,4 +1,8 @@
-"""Binary classification metrics on the device: MLlib 1.6.1's BinaryClassificationMetrics with
+"""Classification metrics on the device. MulticlassMetrics (the end of this file): the K x K
+confusion table of psgd_confusion_device / psgd_confusion_model_device and MLlib 1.6.1's members
+derived from it on the host.
+
+Binary classification metrics: MLlib 1.6.1's BinaryClassificationMetrics with
 numBins = 0 -- the step every classification example of the linear-methods guide ends with
 (`new BinaryClassificationMetrics(scoreAndLabels).areaUnderROC()`).
 
@@ -13,7 +17,7 @@ import numpy as np
 from . import _native as N
 from ._native import IllegalArgumentException, UnsupportedOperationException
 
-__all__ = ["BinaryClassificationMetrics", "SORT_TILE"]
+__all__ = ["BinaryClassificationMetrics", "MulticlassMetrics", "SORT_TILE"]
 
 
 def __getattr__(name):
@@ -260,3 +264,171 @@ def _check_bins(numBins):
     if numBins > 0:
         raise UnsupportedOperationException(
             "numBins > 0 is not built: MLlib's down-sampling of the curves follows its range partitioning")
+
+
+class MulticlassMetrics:
+    """Evaluator for multiclass classification: MulticlassMetrics(predictionAndLabels).
+
+    predictions and labels are host arrays or device tensors of equal length holding classes as
+    doubles (whole numbers in [0, numClasses)); numClasses defaults to the largest value + 1, found
+    on the device. The pairs are counted on the device into a K x K table of int64 (rows actual,
+    columns predicted; psgd_confusion_device, integer atomics: exact); every member below is
+    arithmetic on that table on the host. A value that is not a whole number in [0, numClasses)
+    raises IllegalArgumentException.
+
+    The definitions are this project's restatement of MLlib 1.6.1's MulticlassMetrics, not pinned to
+    its source: `labels` are the classes that occur as a true label, ascending (MLlib takes them
+    from labelCountByClass); confusionMatrix() is over those only, so a predicted class that never
+    occurs as a label has no column, but it still counts as a false positive of its class and as a
+    miss of the row's label. A zero denominator gives 0.0 where MLlib guards it (precision with
+    tp + fp = 0, fMeasure with p + r = 0). The per-label members raise for a class that never occurs
+    as a label (MLlib: NoSuchElementException)."""
+
+    def __init__(self, predictions, labels, numClasses=None):
+        if _length(predictions) != _length(labels):
+            raise IllegalArgumentException(
+                f"requirement failed: predictions and labels differ in length: {_length(predictions)} and "
+                f"{_length(labels)}")
+        import torch
+        from .optimization import get_context
+        if not torch.cuda.is_available():
+            raise N.DeviceError("MulticlassMetrics needs a visible MI355X (torch.cuda.is_available() is False)")
+        dev = predictions.device if torch.is_tensor(predictions) and predictions.is_cuda else torch.device(
+            "cuda", torch.cuda.current_device())
+        ctx = get_context(dev.index if dev.index is not None else torch.cuda.current_device())
+        caller = torch.cuda.current_stream(dev)
+        stream = torch.cuda.Stream(device=dev)   # a real handle: NULL would select the library's own stream
+        stream.wait_stream(caller)
+        with torch.cuda.stream(stream):
+            p, y = _vector(torch, predictions, dev, "predictions"), _vector(torch, labels, dev, "labels")
+            n = int(p.shape[0])
+            if numClasses is None:
+                top = float(torch.maximum(p.max(), y.max()).item()) if n else 0.0
+                if not np.isfinite(top) or top < 0.0:
+                    raise IllegalArgumentException(f"requirement failed: classes must be whole numbers >= 0, got {top!r}")
+                numClasses = int(top) + 1
+            K = int(numClasses)
+            if K < 1:
+                raise IllegalArgumentException(f"requirement failed: numClasses must be positive but got {K}")
+            buf = torch.zeros(1 + K * K, dtype=torch.int64, device=dev)   # {n_bad, counts}
+            ctx.confusion_device(p.data_ptr() if n else None, y.data_ptr() if n else None, n, K, buf.data_ptr() + 8,
+                                 buf.data_ptr(), stream.cuda_stream)
+            h = buf.cpu().numpy()
+        caller.wait_stream(stream)
+        if int(h[0]) > 0:
+            raise IllegalArgumentException(
+                f"requirement failed: {int(h[0])} (prediction, label) pairs hold a value that is not a whole "
+                f"number in [0, {K})")
+        self._set(h[1:].reshape(K, K))
+
+    def _set(self, table):
+        t = np.ascontiguousarray(table, dtype=np.int64)
+        if t.ndim != 2 or t.shape[0] != t.shape[1] or np.any(t < 0):
+            raise IllegalArgumentException("requirement failed: the confusion table must be square and non-negative")
+        self.table = t                                   # [K, K] over every class
+        self.numClasses = int(t.shape[0])
+        self._label_count = t.sum(axis=1)                # labelCountByClass
+        self._pred_count = t.sum(axis=0)
+        self._n = int(t.sum())
+        self.labels = np.flatnonzero(self._label_count > 0).astype(np.float64)
+
+    @classmethod
+    def fromTable(cls, table) -> "MulticlassMetrics":
+        """From a K x K table already on the host (rows actual, columns predicted). Needs no device."""
+        self = cls.__new__(cls)
+        self._set(table)
+        return self
+
+    @classmethod
+    def fromModel(cls, data, weights, numClasses: int, *, engine=None) -> "MulticlassMetrics":
+        """The metrics of a multinomial logistic model ((numClasses - 1) * num_features weights) on
+        `data`: the rows are scored where they are registered, the classes stay in device scratch
+        and the labels are the registry's (psgd_confusion_model_device). With several ranks each
+        counts its own partitions and the tables are added."""
+        from .optimization import HipEngine, _dist, _weights_size, check_multinomial_weights, check_num_classes
+        K = check_num_classes(numClasses)
+        if data.num_partitions == 0:
+            return cls.fromTable(np.zeros((K, K), dtype=np.int64))
+        check_multinomial_weights(K, data.num_features, _weights_size(weights))
+        if engine is None:
+            rank, world, _ = _dist()
+            engine = HipEngine(data, rank, world)
+        return cls.fromTable(engine.confusion(K, weights))
+
+    # the table ---------------------------------------------------------------------------------
+    def confusionMatrix(self) -> np.ndarray:
+        """Rows actual, columns predicted, over `labels` only."""
+        idx = self.labels.astype(np.int64)
+        return self.table[np.ix_(idx, idx)].copy()
+
+    def _class(self, label) -> int:
+        c = int(label)
+        if c != label or not (0 <= c < self.numClasses) or self._label_count[c] == 0:
+            raise IllegalArgumentException(f"requirement failed: class {label!r} does not occur as a label")
+        return c
+
+    def _tp(self, c: int) -> int:
+        return int(self.table[c, c])
+
+    def _fp(self, c: int) -> int:
+        return int(self._pred_count[c]) - self._tp(c)
+
+    # per label -----------------------------------------------------------------------------------
+    def truePositiveRate(self, label) -> float:
+        return self.recall(label)
+
+    def falsePositiveRate(self, label) -> float:
+        c = self._class(label)
+        den = self._n - int(self._label_count[c])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return float(np.float64(self._fp(c)) / np.float64(den))
+
+    def precision(self, label=None) -> float:
+        if label is None:
+            return self._accuracy()
+        c = self._class(label)
+        tp, fp = self._tp(c), self._fp(c)
+        return 0.0 if tp + fp == 0 else tp / (tp + fp)
+
+    def recall(self, label=None) -> float:
+        if label is None:
+            return self._accuracy()
+        c = self._class(label)
+        return self._tp(c) / int(self._label_count[c])
+
+    def fMeasure(self, label=None, beta: float = 1.0) -> float:
+        if label is None:
+            return self._accuracy()
+        p, r = self.precision(label), self.recall(label)
+        b2 = float(beta) * float(beta)
+        return 0.0 if p + r == 0 else (1 + b2) * p * r / (b2 * p + r)
+
+    # over all rows -------------------------------------------------------------------------------
+    def _accuracy(self) -> float:
+        """Correct predictions / rows (NaN without rows: 0.0 / 0)."""
+        return float(np.trace(self.table)) / self._n if self._n else float("nan")
+
+    def _weighted(self, member) -> float:
+        total = 0.0
+        for label in self.labels:
+            total = total + member(label) * int(self._label_count[int(label)]) / self._n
+        return total
+
+    @property
+    def weightedTruePositiveRate(self) -> float:
+        return self.weightedRecall
+
+    @property
+    def weightedFalsePositiveRate(self) -> float:
+        return self._weighted(self.falsePositiveRate)
+
+    @property
+    def weightedRecall(self) -> float:
+        return self._weighted(self.recall)
+
+    @property
+    def weightedPrecision(self) -> float:
+        return self._weighted(self.precision)
+
+    def weightedFMeasure(self, beta: float = 1.0) -> float:
+        return self._weighted(lambda label: self.fMeasure(label, beta))

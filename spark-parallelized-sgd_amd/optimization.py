@@ -423,8 +423,16 @@ class HipEngine(ShardedEngine):
         partitions contributes zeros. Every registered row counts, whatever an earlier epoch sampled."""
         if num_classes(gradient) > 2:
             raise N.UnsupportedOperationException(
-                "evaluate with the multinomial LogisticGradient (numClasses > 2) is not built")
+                "evaluate with the multinomial LogisticGradient (numClasses > 2) is not built: "
+                "use evaluate_multinomial")
         kind = gradient_kind(gradient)
+        return self._score_all(self._score_weights, w, lambda w_ptr, out3, part: self.ctx.evaluate_device(
+            kind, w_ptr, out3, part, self.stream.cuda_stream))
+
+    def _score_all(self, to_device, w, enqueue) -> "EngineScore":
+        """The frame of evaluate / evaluate_multinomial: w through to_device on self.stream,
+        enqueue(w_ptr, out3_ptr, part_ptr) for this rank's partitions, the ranks' all-gather and
+        the sums in rank order."""
         torch = self.torch
         P = self._data.num_partitions
         shards = [shard_range(P, r, self.world) for r in range(self.world)]
@@ -432,14 +440,13 @@ class HipEngine(ShardedEngine):
         caller = torch.cuda.current_stream(self.dev)
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream):
-            w_dev = self._score_weights(w)
+            w_dev = to_device(w)
             buf = torch.zeros(width, dtype=torch.float64, device=self.dev)
             if self.n_local > 0:
                 with self.ctx.engine_lock:
                     if self.ctx.registered_token != self._key:
                         self._register(self._data)
-                    self.ctx.evaluate_device(kind, w_dev.data_ptr(), buf.data_ptr(), buf.data_ptr() + 24,
-                                             self.stream.cuda_stream)
+                    enqueue(w_dev.data_ptr(), buf.data_ptr(), buf.data_ptr() + 24)
             if self.world > 1:
                 import torch.distributed as dist
                 out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
@@ -485,6 +492,94 @@ class HipEngine(ShardedEngine):
         out.record_stream(caller)
         keep.synchronize()   # w_dev may be a temporary of this call
         return out
+
+    # scoring a multinomial logistic model (psgd_evaluate_multinomial_device and its kin) ----------
+    def _multinomial_weights(self, numClasses: int):
+        """to_device for (K - 1) * num_features weights (MLlib's require on weights.size)."""
+        nf, K = self._data.num_features, int(numClasses)
+
+        def to_device(w):
+            if self.torch.is_tensor(w):
+                w_dev = w.detach().to(device=self.dev, dtype=self.torch.float64).contiguous()
+            else:
+                w_dev = self.torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.dev)
+            check_multinomial_weights(K, nf, int(w_dev.numel()) if w_dev.dim() == 1 else -1)
+            return w_dev
+        return to_device
+
+    def evaluate_multinomial(self, numClasses: int, w) -> "EngineScore":
+        """evaluate() for LogisticGradient(numClasses = K > 2): lossSum, count and nCorrect (rows
+        whose predictPoint class equals the label) of the (K - 1) * num_features weights w over
+        every partition, on all ranks, with the per-partition sums
+        (psgd_evaluate_multinomial_device). The same all-gather and rank-order sums as evaluate()."""
+        K = check_num_classes(numClasses)
+        return self._score_all(self._multinomial_weights(K), w,
+                               lambda w_ptr, out3, part: self.ctx.evaluate_multinomial_device(
+                                   K, w_ptr, out3, part, self.stream.cuda_stream))
+
+    def predict_classes(self, p: int, numClasses: int, w, margins: bool = False):
+        """The predicted classes of local partition p's rows as a device tensor of doubles (the
+        labels' convention), in iterator order; with margins=True also the raw margins [n, K - 1]
+        (psgd_predict_multinomial_device)."""
+        K = check_num_classes(numClasses)
+        if not (self.lo <= p < self.hi):
+            raise IllegalArgumentException(
+                f"requirement failed: partition {p} is not held by rank {self.rank} "
+                f"(its partitions are [{self.lo}, {self.hi}))")
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            w_dev = self._multinomial_weights(K)(w)
+            n = self._data.partitions[p].n_rows
+            classes = torch.empty(n, dtype=torch.float64, device=self.dev)
+            m = torch.empty((n, K - 1), dtype=torch.float64, device=self.dev) if margins else None
+            with self.ctx.engine_lock:
+                if self.ctx.registered_token != self._key:
+                    self._register(self._data)
+                self.ctx.predict_multinomial_device(p, K, w_dev.data_ptr(), classes.data_ptr(),
+                                                    m.data_ptr() if margins else None, self.stream.cuda_stream)
+            keep = torch.cuda.Event()
+            keep.record(self.stream)
+        caller.wait_stream(self.stream)
+        classes.record_stream(caller)
+        if margins:
+            m.record_stream(caller)
+        keep.synchronize()   # w_dev may be a temporary of this call
+        return (classes, m) if margins else classes
+
+    def confusion(self, numClasses: int, w) -> np.ndarray:
+        """The K x K confusion table (rows actual, columns predicted; int64) of weights w over every
+        partition, on all ranks (psgd_confusion_model_device: the classes go to the context's scratch,
+        the labels are read where the registry holds them). Several ranks all-gather their tables and
+        add them: integers, exact in any order. A label that is not a whole number in [0, K) raises."""
+        K = check_num_classes(numClasses)
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            w_dev = self._multinomial_weights(K)(w)
+            buf = torch.zeros(1 + K * K, dtype=torch.int64, device=self.dev)   # {n_bad, counts}
+            if self.n_local > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    self.ctx.confusion_model_device(K, w_dev.data_ptr(), buf.data_ptr() + 8, buf.data_ptr(),
+                                                    self.stream.cuda_stream)
+            if self.world > 1:
+                import torch.distributed as dist
+                out = torch.empty(self.world * (1 + K * K), dtype=torch.int64, device=self.dev)
+                if dist.get_backend() == "gloo":
+                    dist.all_gather(list(out.view(self.world, 1 + K * K).unbind(0)), buf)
+                else:
+                    dist.all_gather_into_tensor(out, buf)
+                h = out.view(self.world, 1 + K * K).sum(dim=0).cpu().numpy()
+            else:
+                h = buf.cpu().numpy()
+        if int(h[0]) > 0:
+            raise IllegalArgumentException(
+                f"requirement failed: {int(h[0])} labels are not whole numbers in [0, {K})")
+        return h[1:].reshape(K, K).astype(np.int64)
 
     # binary classification metrics (psgd_binary_counts_model_device / psgd_binary_counts_device) --
     def _local_scores(self, w_dev):
@@ -865,10 +960,11 @@ def evaluate(data: PartitionedData, gradient: Gradient, updater: SGDUpdater, reg
     scoring the training set after training copies nothing. Scoring another PartitionedData (a
     held-out set) registers it in the training set's place, as any second engine on the device
     does; training on the first set afterwards registers that one again. The multinomial
-    LogisticGradient (numClasses > 2) raises UnsupportedOperationException."""
+    LogisticGradient (numClasses > 2) raises UnsupportedOperationException: evaluate_multinomial scores it."""
     if num_classes(gradient) > 2:
         raise N.UnsupportedOperationException(
-            "evaluate with the multinomial LogisticGradient (numClasses > 2) is not built")
+            "evaluate with the multinomial LogisticGradient (numClasses > 2) is not built: "
+            "use evaluate_multinomial")
     gradient_kind(gradient)
     classifier = not isinstance(gradient, LeastSquaresGradient)
     if data.num_partitions == 0:
@@ -882,6 +978,53 @@ def evaluate(data: PartitionedData, gradient: Gradient, updater: SGDUpdater, reg
     regVal = engine.initial_regval(params, np.ascontiguousarray(w_host, dtype=np.float64))
     return Evaluation(score.lossSum, score.count, score.nCorrect if classifier else None, regVal,
                       score.partLoss, score.partCorrect)
+
+
+def check_num_classes(numClasses) -> int:
+    """K of the multinomial scoring calls: an integer > 2."""
+    K = int(numClasses)
+    if K < 3:
+        raise IllegalArgumentException(
+            f"requirement failed: the multinomial scoring calls need numClasses > 2 but got {K} "
+            "(a binary model goes through evaluate / predict)")
+    return K
+
+
+def check_multinomial_weights(K: int, num_features: int, size: int) -> None:
+    """LogisticGradient.compute: require(weights.size % dataSize == 0 &&
+    numClasses == weights.size / dataSize + 1) [ext MLlib 1.6.1]."""
+    if num_features == 0 or size < 0 or size % num_features != 0 or K != size // num_features + 1:
+        raise IllegalArgumentException("requirement failed")
+
+
+def _weights_size(weights) -> int:
+    shape = tuple(weights.shape) if hasattr(weights, "shape") else np.asarray(weights).shape
+    return int(shape[0]) if len(shape) == 1 else -1
+
+
+def evaluate_multinomial(data: PartitionedData, gradient: Gradient, updater: SGDUpdater, regParam: float, weights,
+                         *, engine=None) -> Evaluation:
+    """evaluate() for LogisticGradient(numClasses = K > 2): score the (K - 1) * num_features
+    `weights` (a host array or a device tensor) on `data` -- the loss of LogisticGradient.compute
+    summed, the accuracy of LogisticRegressionModel.predict's classes (the pivot class 0 unless a
+    margin is positive; exact ties to the lowest class) and regVal as evaluate() defines it. The
+    rows are scored where they are registered; a binary gradient raises IllegalArgumentException."""
+    if not isinstance(gradient, LogisticGradient) or num_classes(gradient) < 3:
+        raise IllegalArgumentException(
+            "requirement failed: evaluate_multinomial needs LogisticGradient(numClasses > 2); "
+            "a binary gradient goes through evaluate")
+    K = num_classes(gradient)
+    if data.num_partitions == 0:
+        return Evaluation(0.0, 0, 0, float("nan"))
+    check_multinomial_weights(K, data.num_features, _weights_size(weights))
+    if engine is None:
+        rank, world, _ = _dist()
+        engine = HipEngine(data, rank, world)
+    score = engine.evaluate_multinomial(K, weights)
+    w_host = engine.to_host(weights) if hasattr(weights, "data_ptr") else np.asarray(weights, dtype=np.float64)
+    params = make_params(gradient, updater, 1.0, regParam, 1.0, 0.0)
+    regVal = engine.initial_regval(params, np.ascontiguousarray(w_host, dtype=np.float64))
+    return Evaluation(score.lossSum, score.count, score.nCorrect, regVal, score.partLoss, score.partCorrect)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -957,6 +1100,10 @@ class ParallelizedSGD:
         and objective at those weights, the accuracy of a classifier, per-partition sums
         (evaluate() below; build extension, the reference's users go through MLlib's models)."""
         return evaluate(data, self.gradient, self.updater, self.regParam, weights, engine=engine)
+
+    def evaluate_multinomial(self, data: PartitionedData, weights, *, engine=None) -> "Evaluation":
+        """evaluate() for this optimizer's LogisticGradient(numClasses > 2) (evaluate_multinomial() below)."""
+        return evaluate_multinomial(data, self.gradient, self.updater, self.regParam, weights, engine=engine)
 
     # object ParallelizedSGD ---------------------------------------------------------------------
     @staticmethod
