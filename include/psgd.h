@@ -339,6 +339,54 @@ int32_t psgd_gradient_sum(psgd_ctx* ctx, int32_t gradient, const double* w, doub
 int32_t psgd_gradient_sum_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double mini_batch_fraction,
                                  int32_t iteration, double* d_out, void* stream);
 
+/* psgd_gradient_sum for LogisticGradient(numClasses = num_classes > 2) at weights w, (K - 1) d long in
+ * K - 1 class blocks W[c d + j] with class 0 the pivot (MLlib 1.6.1 Gradient.scala, numClasses > 2):
+ * per batch row, margins m_c = x . W_c, M = max_c m_c (first index on ties; when M > 0 every margin
+ * is shifted by M and the sum takes exp(-M) in the maximum's place),
+ *   mult_c = exp(m_c [- M]) / (sum + 1) - [y != 0 and y == c + 1],
+ * and the loss of psgd_evaluate_multinomial (label.toInt; a label that is no class matches no
+ * indicator and is not an error). The output is (K - 1) d + 2 doubles:
+ *   out[c d + j]          gradientSum = sum_i mult_ic x_ij,
+ *   out[(K - 1) d]        lossSum,
+ *   out[(K - 1) d + 1]    (double)count.
+ * fp64 whatever the storage; zero values and non-finite weights as the scoring calls treat them.
+ * The batch, the ordering, the scratch and the untouched epoch state are psgd_gradient_sum's.
+ * Reproducibility: dense rows are summed without floating-point atomics in an order fixed by the
+ * registry's geometry and K -- every output has the same bits from call to call, on either dense
+ * path (PSGD_GRAD_MN_TWO_PASS=1, read at every call, sends a shape that would run the fused kernel
+ * down the general two-pass path; the two paths agree to rounding, not bit for bit; the fused kernel
+ * runs where it was measured faster, PSGD_GRAD_MN_FUSE_ALL=1 runs it wherever its accumulators fit
+ * the registers). CSR rows:
+ * lossSum and count are reproducible; gradientSum is added with fp64 vector atomics and may differ
+ * in its last bits from run to run (PSGD_GRAD_CSR_GLOBAL=1 forces the global-atomic path here too).
+ * Errors: PSGD_EINVAL for a null ctx or pointer, num_classes < 3 or a fraction outside [0, 1];
+ * PSGD_EUNSUPPORTED past 4,097 classes; PSGD_ESTATE when no partition is registered. A registry of
+ * empty partitions or an empty batch gives zeros. psgd_gd_update takes d = (K - 1) d unchanged. */
+int32_t psgd_gradient_sum_multinomial(psgd_ctx* ctx, int32_t num_classes, const double* w,
+                                      double mini_batch_fraction, int32_t iteration, double* out);
+int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w,
+                                             double mini_batch_fraction, int32_t iteration, double* d_out,
+                                             void* stream);
+
+/* Which kernels psgd_gradient_sum_multinomial runs for rows of `layout` (0 dense, 1 CSR), `storage`
+ * (psgd_dtype), d features, num_classes and (CSR) a longest row of max_nnz entries: host code, no
+ * device and no context. out[PSGD_MN_PLAN_LEN] receives
+ *   [0] the path: 0 dense fused, 1 dense general (two passes), 2 CSR with the accumulator in LDS,
+ *       3 CSR with global atomics;
+ *   [1] lanes across a row (fused kernel / multiplier pass / CSR);
+ *   [2] 1 when the margins read the class blocks from LDS;
+ *   [3] the softmax shape: 0 a lane takes a row (K - 1 <= 64), 1 the lanes go across the classes;
+ *   [4] rows of a tile;
+ *   [5] fused: 16-byte row vectors a lane owns; [6] fused: class accumulators a lane keeps;
+ *   [7] general, accumulation pass: lanes across a column chunk; [8] its column chunks; [9] its
+ *       class chunks; [10] consecutive tiles a gradient record covers; [11] tiles of a row range.
+ * It honours PSGD_GRAD_MN_TWO_PASS and PSGD_GRAD_CSR_GLOBAL as the call does. Errors: PSGD_EINVAL
+ * for a null out, an unknown layout or storage, d <= 0, max_nnz < 0 or num_classes < 3;
+ * PSGD_EUNSUPPORTED past 4,097 classes. */
+#define PSGD_MN_PLAN_LEN 12
+int32_t psgd_gradient_multinomial_plan(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
+                                       int64_t max_nnz, int32_t* out);
+
 /* One GradientDescent update from a psgd_gradient_sum result `sum` (d + 2 doubles):
  *   (w_out, *regval_out) = updater.compute(w, sum[0 .. d) / sum[d + 1], step_size, iteration, reg_param)
  * for the stateless updaters, MLlib's SimpleUpdater / SquaredL2Updater / L1Updater, with

@@ -16,7 +16,8 @@ from .gradient import Gradient, HingeGradient, LeastSquaresGradient, LogisticGra
 from .feature import StandardScaler, StandardScalerModel, column_stats
 from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine, ParallelizedSGD, ShardedEngine,
                            evaluate, evaluate_multinomial, make_params, runParallelizedSGD)
-from .gradient_descent import GradientDescent, GradientSum, gradient_sum, runMiniBatchSGD
+from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradient_sum_multinomial, runMiniBatchSGD,
+                               runMiniBatchSGDMultinomial)
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
@@ -27,6 +28,7 @@ __all__ = [
     "ParallelizedSGD", "runParallelizedSGD", "evaluate", "evaluate_multinomial", "Evaluation", "HipEngine",
     "BinaryClassificationMetrics", "MulticlassMetrics", "randomSplit", "kFold",
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
+    "gradient_sum_multinomial", "runMiniBatchSGDMultinomial",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",
     "SGDUpdater", "SimpleSGDUpdater", "SquaredL2SGDUpdater", "L1SGDUpdater",

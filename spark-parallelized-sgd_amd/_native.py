@@ -32,6 +32,7 @@ EXPORTED = (
     "psgd_evaluate", "psgd_evaluate_device", "psgd_predict", "psgd_predict_device",
     "psgd_column_stats", "psgd_column_stats_device", "psgd_transform_columns", "psgd_transform_columns_device",
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
+    "psgd_gradient_sum_multinomial", "psgd_gradient_sum_multinomial_device", "psgd_gradient_multinomial_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
     "psgd_evaluate_multinomial", "psgd_evaluate_multinomial_device",
@@ -139,6 +140,9 @@ def lib():
             "psgd_transform_columns_device": ([vp, vp, vp, vp], C.c_int32),
             "psgd_gradient_sum": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp], C.c_int32),
             "psgd_gradient_sum_device": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp, vp], C.c_int32),
+            "psgd_gradient_sum_multinomial": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp], C.c_int32),
+            "psgd_gradient_sum_multinomial_device": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp, vp], C.c_int32),
+            "psgd_gradient_multinomial_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
             "psgd_gd_update": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, dp],
                                C.c_int32),
             "psgd_gd_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp,
@@ -219,6 +223,23 @@ def multiclass_switches() -> dict:
     out = (C.c_int32 * 3)()
     check(lib().psgd_multiclass_switches(out))
     return {"lds_weights": int(out[0]), "lane_classes": int(out[1]), "confusion_lds_cells": int(out[2])}
+
+
+MN_GRAD_PATHS = ("fused", "general", "csr_lds", "csr_global")   # psgd_gradient_multinomial_plan's out[0]
+
+
+def gradient_multinomial_plan(layout: str, storage: str, d: int, num_classes: int, max_nnz: int = 0) -> dict:
+    """Which kernels psgd_gradient_sum_multinomial runs for rows of `layout` ("dense" / "csr") stored
+    as `storage` ("f32" / "f64"), with the environment switches as they are now
+    (psgd_gradient_multinomial_plan: host code, no device)."""
+    out = (C.c_int32 * 12)()
+    check(lib().psgd_gradient_multinomial_plan({"dense": 0, "csr": 1}[layout], {"f64": 0, "f32": 1}[storage],
+                                               int(d), int(num_classes), int(max_nnz), out))
+    keys = ("path", "group", "weights_in_lds", "wide_softmax", "tile_rows", "nvl", "class_accumulators",
+            "acc_group", "col_chunks", "class_chunks", "span", "range")
+    plan = {k: int(v) for k, v in zip(keys, out)}
+    plan["path"] = MN_GRAD_PATHS[plan["path"]]
+    return plan
 
 
 class _PinnedBuffer:
@@ -516,6 +537,21 @@ class Context:
         """psgd_gradient_sum_device: enqueued on `stream`; out[d + 2] on the device."""
         check(self._L.psgd_gradient_sum_device(self.handle, int(gradient), w_ptr, float(fraction), int(iteration),
                                                out_ptr, stream))
+
+    def gradient_sum_multinomial(self, num_classes: int, w, fraction: float = 1.0, iteration: int = 0):
+        """Host-pointer form (psgd_gradient_sum_multinomial): the (K - 1) d + 2 doubles {gradientSum,
+        lossSum, count} of the (K - 1) d host weights w over the batch."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        out = np.zeros(w.shape[0] + 2, dtype=np.float64)
+        check(self._L.psgd_gradient_sum_multinomial(self.handle, int(num_classes), w.ctypes.data, float(fraction),
+                                                    int(iteration), out.ctypes.data))
+        return out
+
+    def gradient_sum_multinomial_device(self, num_classes: int, w_ptr, fraction, iteration, out_ptr, stream=None):
+        """psgd_gradient_sum_multinomial_device: enqueued on `stream`; out[(K - 1) d + 2] on the device."""
+        check(self._L.psgd_gradient_sum_multinomial_device(self.handle, int(num_classes), w_ptr, float(fraction),
+                                                           int(iteration), out_ptr, stream))
 
     def gd_update(self, updater: int, w, gsum, step: float, iteration: int, reg: float):
         """Host-pointer form (psgd_gd_update): (w', regVal) of one GradientDescent update."""

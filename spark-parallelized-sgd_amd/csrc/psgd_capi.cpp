@@ -2308,6 +2308,37 @@ static int32_t gradient_args(int32_t gradient, double fraction) {
     return PSGD_OK;
 }
 
+// The descriptors of the batch (ctx->mu held, score_prepare done): the registered ones, or for
+// 0 < fraction < 1 the sampled ones in the batch calls' own buffers.
+static int32_t gradient_batch(psgd_ctx* ctx, double mini_batch_fraction, int32_t iteration, hipStream_t st,
+                              const psgd::ChainDesc** out) {
+    const int P = (int)ctx->parts.size();
+    int64_t n_max = 0;
+    for (auto& kv : ctx->parts) n_max = std::max(n_max, kv.second.n_rows);
+    const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>();
+    if (mini_batch_fraction < 1.0) {
+        // the sampled batch's row indices are int32 (ChainDesc::rows)
+        if (n_max > (int64_t)INT32_MAX)
+            return fail(PSGD_EUNSUPPORTED, "miniBatchFraction < 1 on a partition of more than 2^31 - 1 rows");
+        const std::vector<uint64_t> xs = sampler_states(ctx, iteration);
+        const int64_t stride = std::max<int64_t>(n_max, 1);
+        HIP_TRY(ctx->gdescs.ensure((size_t)P * sizeof(psgd::ChainDesc)));
+        HIP_TRY(ctx->grows.ensure((size_t)P * (size_t)stride * sizeof(int32_t)));
+        HIP_TRY(ctx->gys.ensure((size_t)P * (size_t)stride * sizeof(double)));
+        HIP_TRY(ctx->gxstate.ensure((size_t)P * sizeof(uint64_t)));
+        HIP_TRY(hipMemcpyAsync(ctx->gxstate.p, xs.data(), (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+        const int e = psgd::launch_sample(descs, ctx->gdescs.as<psgd::ChainDesc>(), ctx->gxstate.as<uint64_t>(),
+                                          mini_batch_fraction, ctx->grows.as<int32_t>(), ctx->gys.as<double>(), stride,
+                                          P, st);
+        if (e) return fail(PSGD_EDEVICE, "sample kernel launch failed");
+        // the sampler states leave a host vector of this call: wait for the copy
+        HIP_TRY(hipStreamSynchronize(st));
+        descs = ctx->gdescs.as<psgd::ChainDesc>();
+    }
+    *out = descs;
+    return PSGD_OK;
+}
+
 int32_t psgd_gradient_sum_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double mini_batch_fraction,
                                  int32_t iteration, double* d_out, void* stream) {
     if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
@@ -2329,31 +2360,11 @@ int32_t psgd_gradient_sum_device(psgd_ctx* ctx, int32_t gradient, const double* 
         HIP_TRY(hipMemsetAsync(d_out, 0, ((size_t)d + 2) * sizeof(double), st));
         return PSGD_OK;
     }
-    int64_t n_max = 0, max_nnz = 0;
-    for (auto& kv : ctx->parts) {
-        n_max = std::max(n_max, kv.second.n_rows);
-        max_nnz = std::max(max_nnz, kv.second.max_nnz);
-    }
-    const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>();
-    if (mini_batch_fraction < 1.0) {
-        // the sampled batch's row indices are int32 (ChainDesc::rows)
-        if (n_max > (int64_t)INT32_MAX)
-            return fail(PSGD_EUNSUPPORTED, "miniBatchFraction < 1 on a partition of more than 2^31 - 1 rows");
-        const std::vector<uint64_t> xs = sampler_states(ctx, iteration);
-        const int64_t stride = std::max<int64_t>(n_max, 1);
-        HIP_TRY(ctx->gdescs.ensure((size_t)P * sizeof(psgd::ChainDesc)));
-        HIP_TRY(ctx->grows.ensure((size_t)P * (size_t)stride * sizeof(int32_t)));
-        HIP_TRY(ctx->gys.ensure((size_t)P * (size_t)stride * sizeof(double)));
-        HIP_TRY(ctx->gxstate.ensure((size_t)P * sizeof(uint64_t)));
-        HIP_TRY(hipMemcpyAsync(ctx->gxstate.p, xs.data(), (size_t)P * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-        const int e = psgd::launch_sample(descs, ctx->gdescs.as<psgd::ChainDesc>(), ctx->gxstate.as<uint64_t>(),
-                                          mini_batch_fraction, ctx->grows.as<int32_t>(), ctx->gys.as<double>(), stride,
-                                          P, st);
-        if (e) return fail(PSGD_EDEVICE, "sample kernel launch failed");
-        // the sampler states leave a host vector of this call: wait for the copy
-        HIP_TRY(hipStreamSynchronize(st));
-        descs = ctx->gdescs.as<psgd::ChainDesc>();
-    }
+    int64_t max_nnz = 0;
+    for (auto& kv : ctx->parts) max_nnz = std::max(max_nnz, kv.second.max_nnz);
+    const psgd::ChainDesc* descs = nullptr;
+    rc = gradient_batch(ctx, mini_batch_fraction, iteration, st, &descs);
+    if (rc) return rc;
     // the statistics passes' tiling (a sampled batch keeps it: its tiles past the batch's end are empty)
     const int64_t n_tiles = ctx->stat_tile0.back();
     const psgd::GradGeom gm = psgd::grad_geometry(first.layout, d, storage, max_nnz, ctx->stat_geom.tile_rows);
@@ -2407,6 +2418,103 @@ int32_t psgd_gradient_sum(psgd_ctx* ctx, int32_t gradient, const double* w, doub
     DeviceGuard g(ctx->device);
     HIP_TRY(hipMemcpyAsync(out, d_out, (d + 2) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+// ---- The batch gradient of the multinomial LogisticGradient (kernels in psgd_grad_mn.hip) ----
+static int32_t gradient_mn_args(int32_t num_classes, double fraction) {
+    if (num_classes < 3)
+        return fail(PSGD_EINVAL, "num_classes must be >= 3 (got " + std::to_string(num_classes) +
+                                     "): psgd_gradient_sum serves the binary LogisticGradient");
+    if (num_classes - 1 > psgd::kMultinomialMaxBlocks)
+        return fail(PSGD_EUNSUPPORTED, "LogisticGradient(numClasses = " + std::to_string(num_classes) +
+                                           ") exceeds the built maximum of " +
+                                           std::to_string(psgd::kMultinomialMaxBlocks + 1) + " classes");
+    return gradient_args(PSGD_GRADIENT_LOGISTIC, fraction);
+}
+
+int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w,
+                                             double mini_batch_fraction, int32_t iteration, double* d_out,
+                                             void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = gradient_mn_args(num_classes, mini_batch_fraction);
+    if (rc) return rc;
+    if (!d_w || !d_out) return fail(PSGD_EINVAL, "d_w/d_out are null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const Part& first = ctx->parts.begin()->second;
+    const int32_t d = first.d;
+    const int P = (int)ctx->parts.size();
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    const size_t len = (size_t)(num_classes - 1) * (size_t)d + 2;
+    if (mini_batch_fraction <= 0.0) {   // RDD.sample(false, 0, .): every partition's batch is empty
+        HIP_TRY(hipMemsetAsync(d_out, 0, len * sizeof(double), st));
+        return PSGD_OK;
+    }
+    int64_t max_nnz = 0;
+    for (auto& kv : ctx->parts) max_nnz = std::max(max_nnz, kv.second.max_nnz);
+    const psgd::ChainDesc* descs = nullptr;
+    rc = gradient_batch(ctx, mini_batch_fraction, iteration, st, &descs);
+    if (rc) return rc;
+    const int64_t n_tiles = ctx->stat_tile0.back();
+    const psgd::MnGradGeom gm = psgd::grad_mn_geometry(first.layout, storage, d, num_classes, max_nnz);
+    HIP_TRY(ctx->grec.ensure((psgd::grad_mn_scratch(gm, n_tiles) + 1) * sizeof(double)));
+    const int e = psgd::launch_gradient_mn(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage, d_w,
+                                           ctx->grec.as<double>(), d_out, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("multinomial gradient launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_gradient_sum_multinomial(psgd_ctx* ctx, int32_t num_classes, const double* w,
+                                      double mini_batch_fraction, int32_t iteration, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = gradient_mn_args(num_classes, mini_batch_fraction);
+    if (rc) return rc;
+    if (!w || !out) return fail(PSGD_EINVAL, "w/out are null");
+    size_t n = 0;
+    double *d_w = nullptr, *d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        n = (size_t)(num_classes - 1) * (size_t)ctx->parts.begin()->second.d;
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->gio.ensure((2 * n + 2) * sizeof(double)));
+        d_w = ctx->gio.as<double>();
+        d_out = d_w + n;
+        HIP_TRY(hipMemcpyAsync(d_w, w, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        // the caller's array is pageable in general: the copy has left it when this returns
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    rc = psgd_gradient_sum_multinomial_device(ctx, num_classes, d_w, mini_batch_fraction, iteration, d_out, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(out, d_out, (n + 2) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_gradient_multinomial_plan(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
+                                       int64_t max_nnz, int32_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (layout != psgd::kDense && layout != psgd::kCsr) return fail(PSGD_EINVAL, "unknown layout " + std::to_string(layout));
+    if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
+    if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
+    if (max_nnz < 0) return fail(PSGD_EINVAL, "max_nnz must be >= 0");
+    const int32_t rc = gradient_mn_args(num_classes, 1.0);
+    if (rc) return rc;
+    const psgd::MnGradGeom gm = psgd::grad_mn_geometry(layout,
+                                                       storage == PSGD_F32 ? 1 : 0, d, num_classes, max_nnz);
+    const int32_t v[PSGD_MN_PLAN_LEN] = {gm.path, gm.group,   gm.wlds,       gm.wide,         gm.tile_rows, gm.nvl,
+                                         gm.cp,   gm.agroup,  gm.n_colchunks, gm.n_classchunks, gm.span,      gm.range};
+    std::memcpy(out, v, sizeof v);
     return PSGD_OK;
 }
 

@@ -33,28 +33,7 @@ namespace psgd {
 namespace {
 
 constexpr int kMnWaves = 8;            // waves of a workgroup (the wide softmax launches fewer)
-constexpr int kMnHold = 8;             // dense: elements of a row a lane holds
-constexpr int kMnRows = 2;             // dense: rows a lane group holds (a weight read serves both)
-constexpr int kMnCsrHold = 4;          // CSR: entries of a row a lane holds
-constexpr int kMnBuf = 384;            // doubles of a wave's margin buffer, row-per-lane softmax
-constexpr int kMnLdsMax = 144 * 1024;  // a workgroup's LDS at most (the wide softmax's buffers)
 constexpr int kConfBlock = 256;
-
-// Double.toInt
-__device__ __forceinline__ int mn_d2i(double x) {
-    if (x != x) return 0;
-    if (x >= 2147483647.0) return 2147483647;
-    if (x <= -2147483648.0) return (-2147483647 - 1);
-    return (int)x;
-}
-
-// The loss from the pieces (Gradient.scala, numClasses > 2): sum is the sum of exponentials of the
-// (shifted) margins, M the maximum margin.
-__device__ __forceinline__ double mn_loss(double sum, double marginY, double M, double y) {
-    double loss = y > 0.0 ? log1p(sum) - marginY : log1p(sum);
-    if (M > 0.0) loss = loss + M;
-    return loss;
-}
 
 // What a wave needs to score the rows its margin buffer holds.
 struct MnOut {
@@ -153,24 +132,6 @@ __device__ __forceinline__ void mn_flush_wide(const double* marg, int n, const M
         for (int q = lane; q < n * C1; q += 64) out[q] = marg[q];
     }
     wave_lds_sync();
-}
-
-// The margin buffer's shape for a partition whose wave pass could take `rpw` groups of `rows` rows:
-// pitch of a row, groups a pass uses (rp <= rpw) and rows the buffer holds before it is scored (nb, a
-// multiple of rp * rows).
-template <bool ROWLANE>
-__device__ __forceinline__ void mn_buffer_shape(int C1, int rpw, int rows, int& pitch, int& rp, int& nb) {
-    if constexpr (ROWLANE) {
-        pitch = C1 | 1;   // odd: the lanes' rows start on different banks
-        int cap = kMnBuf / pitch;
-        cap = cap > 64 ? 64 : cap;
-        rp = cap / rows < rpw ? cap / rows : rpw;
-        nb = (cap / (rp * rows)) * (rp * rows);
-    } else {
-        pitch = C1;
-        rp = 1;
-        nb = rows;
-    }
 }
 
 // Dense rows. d features, C1 = K - 1 class blocks; mb = doubles of a wave's margin buffer; wpad =

@@ -34,6 +34,7 @@
 #include <cstdlib>
 
 #include "psgd_device.h"
+#include "psgd_eval.h"
 
 namespace psgd {
 namespace {
@@ -43,32 +44,6 @@ constexpr int kGradWaves = kGradBlock / 64;
 constexpr int kGradMaxNvl = 8;       // fused: at most this many 16-byte vectors of a row a lane
 constexpr int kGradChunkVecs = 2;    // two-pass: vectors a lane owns of a column chunk (stats_dense's)
 constexpr int kGradLdsFeatures = 6144;   // CSR: fp64 accumulators a workgroup keeps in LDS (48 KiB)
-
-__device__ __forceinline__ double group_sum(double v, int gl) {
-    if (gl > 1) v = v + dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-    if (gl > 2) v = v + dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-    if (gl > 4) v = v + dpp_mov<0x141>(v);   // row_half_mirror
-    if (gl > 8) v = v + dpp_mov<0x140>(v);   // row_mirror
-    if (gl > 16) v = swap_sum16(v);
-    if (gl > 32) v = swap_sum32(v);
-    return v;
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// The tile's partition: the last p with tile0[p] <= tile. Wave-uniform.
-__device__ __forceinline__ int tile_partition(const int64_t* tile0, int P, int64_t tile) {
-    int lo = 0, hi = P;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (tile0[mid] <= tile) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // buf[0 .. n) holds the dots of batch rows row0 .. row0 + n (n <= 64): lane i < n replaces dot i by
 // row i's multiplier and adds its loss to loss_acc; rows at or past r1 get multiplier 0.
@@ -543,13 +518,6 @@ __global__ __launch_bounds__(64) void gd_regval(const double* __restrict__ part,
     }
 }
 
-unsigned balanced_blocks(int64_t n_items, int num_cus, int per_cu) {
-    const int64_t cap = (int64_t)(num_cus > 0 ? num_cus : 256) * per_cu * kGradWaves;
-    const int64_t rounds = (n_items + cap - 1) / cap;
-    const int64_t waves = (n_items + rounds - 1) / rounds;
-    return (unsigned)((waves + kGradWaves - 1) / kGradWaves);
-}
-
 unsigned column_blocks(int64_t n) { return (unsigned)((n + kGradBlock - 1) / kGradBlock); }
 
 template <typename S, int GRAD>
@@ -572,13 +540,13 @@ template <typename S, int GRAD>
 int launch_dense_sg(const GradGeom& gm, int num_cus, hipStream_t st, const ChainDesc* descs, const int64_t* tile0,
                     int P, int64_t n_tiles, const double* w, double* rec, double* mult) {
     // (the fused kernel's accumulators and rows in flight leave room for two workgroups a CU)
-    if (gm.fused) return launch_fused<S, GRAD>(gm, balanced_blocks(n_tiles, num_cus, 2), st, descs, tile0, P, n_tiles, w, rec);
-    hipLaunchKernelGGL((grad_rowmult<S, GRAD>), dim3(balanced_blocks(n_tiles, num_cus, 8)), dim3(kGradBlock), 0, st,
+    if (gm.fused) return launch_fused<S, GRAD>(gm, grad_balanced_blocks(n_tiles, num_cus, 2), st, descs, tile0, P, n_tiles, w, rec);
+    hipLaunchKernelGGL((grad_rowmult<S, GRAD>), dim3(grad_balanced_blocks(n_tiles, num_cus, 8)), dim3(kGradBlock), 0, st,
                        descs, tile0, P, n_tiles, gm, w, mult, rec);
     int e = (int)hipGetLastError();
     if (e) return e;
     const int64_t n_items = n_tiles * gm.n_chunks;
-    hipLaunchKernelGGL(grad_wsum<S>, dim3(balanced_blocks(n_items, num_cus, 8)), dim3(kGradBlock), 0, st, descs, tile0,
+    hipLaunchKernelGGL(grad_wsum<S>, dim3(grad_balanced_blocks(n_items, num_cus, 8)), dim3(kGradBlock), 0, st, descs, tile0,
                        P, n_items, gm, mult, rec);
     return (int)hipGetLastError();
 }
@@ -617,8 +585,17 @@ int launch_csr_s(int gradient, const GradGeom& gm, bool lds, unsigned blocks, hi
     return -2;
 }
 
+}  // namespace
+
+unsigned grad_balanced_blocks(int64_t n_items, int num_cus, int per_cu) {
+    const int64_t cap = (int64_t)(num_cus > 0 ? num_cus : 256) * per_cu * kGradWaves;
+    const int64_t rounds = (n_items + cap - 1) / cap;
+    const int64_t waves = (n_items + rounds - 1) / rounds;
+    return (unsigned)((waves + kGradWaves - 1) / kGradWaves);
+}
+
 // records [T][W] -> dst[W] in two levels (rec2: [n_spans][W])
-int merge_records(const double* rec, int64_t T, int64_t W, double* rec2, double* dst, hipStream_t st) {
+int grad_merge_records(const double* rec, int64_t T, int64_t W, double* rec2, double* dst, hipStream_t st) {
     const int64_t span = grad_merge_span(T);
     const int64_t n_spans = (T + span - 1) / span;
     hipLaunchKernelGGL(grad_merge, dim3(column_blocks(W), (unsigned)n_spans), dim3(kGradBlock), 0, st, rec, T, span,
@@ -628,8 +605,6 @@ int merge_records(const double* rec, int64_t T, int64_t W, double* rec2, double*
     hipLaunchKernelGGL(grad_merge, dim3(column_blocks(W), 1), dim3(kGradBlock), 0, st, rec2, n_spans, n_spans, dst, W, W);
     return (int)hipGetLastError();
 }
-
-}  // namespace
 
 GradGeom grad_geometry(int layout, int d, int storage, int64_t max_nnz, int tile_rows) {
     GradGeom gm{};
@@ -679,7 +654,7 @@ int launch_gradient_dense(const ChainDesc* descs, const int64_t* tile0, int n_pa
     const int e = storage == 1 ? launch_dense_s<float>(gradient, gm, num_cus, st, descs, tile0, n_parts, n_tiles, w, rec, mult)
                                : launch_dense_s<double>(gradient, gm, num_cus, st, descs, tile0, n_parts, n_tiles, w, rec, mult);
     if (e) return e;
-    return merge_records(rec, n_tiles, (int64_t)gm.d + 2, rec2, out, st);
+    return grad_merge_records(rec, n_tiles, (int64_t)gm.d + 2, rec2, out, st);
 }
 
 int launch_gradient_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
@@ -689,11 +664,11 @@ int launch_gradient_csr(const ChainDesc* descs, const int64_t* tile0, int n_part
     int e = (int)hipMemsetAsync(out, 0, ((size_t)gm.d + 2) * sizeof(double), st);
     if (e || n_tiles <= 0) return e;
     // LDS accumulators: 48 KiB a workgroup at most, so three workgroups a CU
-    const unsigned blocks = balanced_blocks(n_tiles, num_cus, lds ? 2 : 8);
+    const unsigned blocks = grad_balanced_blocks(n_tiles, num_cus, lds ? 2 : 8);
     e = storage == 1 ? launch_csr_s<float>(gradient, gm, lds, blocks, st, descs, tile0, n_parts, n_tiles, w, out, rec)
                      : launch_csr_s<double>(gradient, gm, lds, blocks, st, descs, tile0, n_parts, n_tiles, w, out, rec);
     if (e) return e;
-    return merge_records(rec, n_tiles, 2, rec2, out + gm.d, st);
+    return grad_merge_records(rec, n_tiles, 2, rec2, out + gm.d, st);
 }
 
 int64_t gd_update_blocks(int d) { return ((int64_t)d + kUpdPerBlock - 1) / kUpdPerBlock; }

@@ -305,6 +305,41 @@ int launch_gradient_dense(const ChainDesc* descs, const int64_t* tile0, int n_pa
 int launch_gradient_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
                         const GradGeom& gm, int storage, int gradient, bool lds, const double* w, double* rec,
                         double* rec2, double* out, int num_cus, hipStream_t st);
+// Workgroups of 4 waves for n_items wave items: whole rounds of at most per_cu workgroups a CU.
+unsigned grad_balanced_blocks(int64_t n_items, int num_cus, int per_cu);
+// Records [T][W] -> dst[W] with grad_merge, in two levels, in record order: spans of
+// grad_merge_span(T) records first (rec2: [n_spans][W]), then the spans.
+int grad_merge_records(const double* rec, int64_t T, int64_t W, double* rec2, double* dst, hipStream_t st);
+
+// ---- The batch gradient of the multinomial LogisticGradient (psgd_grad_mn.hip) ----
+// Which kernels a call runs and their geometry: host code, no device (psgd_gradient_multinomial_plan
+// reports it). The tiling is the statistics passes'.
+enum MnGradPath { kMnGradFused = 0, kMnGradGeneral = 1, kMnGradCsrLds = 2, kMnGradCsrGlobal = 3 };
+struct MnGradGeom {
+    int32_t d, C1;        // features, K - 1
+    int32_t tile_rows;
+    int32_t path;         // MnGradPath
+    int32_t nvec;         // dense: 16-byte vectors that hold a row's d features
+    int32_t group;        // lanes across a row: fused kernel / multiplier pass / CSR (16, 32, 64 by the longest row)
+    int32_t nvl, cp;      // fused: vectors of a row a lane owns; class accumulators it keeps (2, 4, 8, 16 >= K - 1)
+    int32_t wlds;         // the margins read the class blocks from LDS
+    int32_t wide;         // softmax with the lanes across the classes (K - 1 > kMnLaneClasses)
+    int32_t agroup;       // general, accumulation pass: lanes across a column chunk (64 / agroup class chunks a wave)
+    int32_t n_colchunks, n_classchunks;
+    int32_t span;         // general: consecutive tiles one gradient record covers (1: a record a tile)
+    int32_t range;        // general: tiles whose multipliers the scratch holds at a time
+};
+// Reads PSGD_GRAD_MN_TWO_PASS and PSGD_GRAD_CSR_GLOBAL. num_classes in [3, kMultinomialMaxBlocks + 1].
+MnGradGeom grad_mn_geometry(int layout, int storage, int d, int num_classes, int64_t max_nnz);
+// Doubles of scratch a call over n_tiles tiles needs (the bound is in psgd_grad_mn.hip's header).
+size_t grad_mn_scratch(const MnGradGeom& gm, int64_t n_tiles);
+// out[(K - 1) d + 2] = {gradientSum, lossSum, count} over the batch rows of descs[0 .. n_parts) at
+// weights w[(K - 1) d]. Dense: no floating-point atomics, reproducible bits. CSR: out[0 .. (K - 1) d)
+// is the accumulator of fp64 atomics.
+int launch_gradient_mn(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
+                       const MnGradGeom& gm, int storage, const double* w, double* scratch, double* out,
+                       int num_cus, hipStream_t st);
+
 // w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
 // the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
 int64_t gd_update_blocks(int d);

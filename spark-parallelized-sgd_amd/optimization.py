@@ -391,7 +391,7 @@ class HipEngine(ShardedEngine):
         return folded[: self.d]
 
     def convergence_terms(self, prev, cur) -> Tuple[float, float]:
-        return self.ctx.convergence_terms_device(self.d, prev.data_ptr(), cur.data_ptr(),
+        return self.ctx.convergence_terms_device(int(cur.shape[0]), prev.data_ptr(), cur.data_ptr(),
                                                  self.stream.cuda_stream)
 
     def to_host(self, w_dev) -> np.ndarray:
@@ -701,24 +701,38 @@ class HipEngine(ShardedEngine):
         tensor of d + 2 doubles (include/psgd.h has the semantics). Each rank runs its partitions; the
         ranks all-gather their d + 2 doubles (the backends of exchange()) and every rank adds the rows
         in rank order (merge_gradient_sums: a loop, not a tree), so all ranks hold the same bits; a
-        rank without partitions contributes zeros. w: a host array or a device tensor."""
+        rank without partitions contributes zeros. w: a host array or a device tensor. The multinomial
+        LogisticGradient (numClasses > 2) goes through gradient_sum_multinomial."""
         if num_classes(gradient) > 2:
             raise N.UnsupportedOperationException(
-                "gradient_sum with the multinomial LogisticGradient (numClasses > 2) is not built")
+                "gradient_sum takes a binary gradient: the multinomial LogisticGradient (numClasses > 2) "
+                "goes through gradient_sum_multinomial")
         kind = gradient_kind(gradient)
+        return self._batch_sum(self._data.num_features + 2, self._score_weights, w,
+                               lambda w_ptr, out: self.ctx.gradient_sum_device(
+                                   kind, w_ptr, miniBatchFraction, iteration, out, self.stream.cuda_stream))
+
+    def gradient_sum_multinomial(self, numClasses: int, w, miniBatchFraction: float = 1.0, iteration: int = 0):
+        """gradient_sum() for LogisticGradient(numClasses = K > 2): a device tensor of
+        (K - 1) * num_features + 2 doubles {gradientSum, lossSum, count} at the (K - 1) * num_features
+        weights w (psgd_gradient_sum_multinomial_device). The same all-gather and rank-order sums."""
+        K = check_num_classes(numClasses)
+        return self._batch_sum((K - 1) * self._data.num_features + 2, self._multinomial_weights(K), w,
+                               lambda w_ptr, out: self.ctx.gradient_sum_multinomial_device(
+                                   K, w_ptr, miniBatchFraction, iteration, out, self.stream.cuda_stream))
+
+    def _batch_sum(self, width: int, to_device, w, call):
         torch = self.torch
-        width = self._data.num_features + 2
         caller = torch.cuda.current_stream(self.dev)
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream):
-            w_dev = self._score_weights(w)
+            w_dev = to_device(w)
             buf = torch.zeros(width, dtype=torch.float64, device=self.dev)
             if self.n_local > 0:
                 with self.ctx.engine_lock:
                     if self.ctx.registered_token != self._key:
                         self._register(self._data)
-                    self.ctx.gradient_sum_device(kind, w_dev.data_ptr(), miniBatchFraction, iteration,
-                                                 buf.data_ptr(), self.stream.cuda_stream)
+                    call(w_dev.data_ptr(), buf.data_ptr())
             if self.world > 1:
                 import torch.distributed as dist
                 out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
