@@ -387,6 +387,52 @@ int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes,
 int32_t psgd_gradient_multinomial_plan(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
                                        int64_t max_nnz, int32_t* out);
 
+/* The augmented Gramian over every registered row -- the second-moment pass behind MLlib 1.6.1's
+ * RowMatrix.computeGramianMatrix / computeCovariance, Statistics.corr and the normal equations of
+ * least squares. With z_i = [x_i0 .. x_i,d-1, y_i, 1] (a = d + 2 columns; the stored values widened to
+ * double, the label as it is) out receives M = sum_i z_i z_i^T: a * a doubles, row-major, both
+ * triangles written, the lower an exact copy of the upper. So
+ *   X^T X = M[0..d, 0..d),  X^T y = M[0..d, d],  y^T y = M[d][d],
+ *   the column sums M[0..d, d + 1],  sum y = M[d][d + 1],  the row count M[d + 1][d + 1] (exact).
+ * All arithmetic is fp64 whatever the storage. A CSR row's absent entries are zeros. NaN and Inf
+ * inputs are outside the contract. The pad columns of a zero-copy row (ld > d) are never read.
+ * d <= PSGD_GRAMIAN_MAX_D (M is at most 134 MB): beyond it PSGD_EUNSUPPORTED.
+ * Reproducibility: dense rows go through v_mfma_f64_16x16x4_f64 without floating-point atomics, in
+ * an order fixed by the registry's geometry and the plan below (never by the grid): every output has
+ * the same bits from call to call. Registering the same rows as more or fewer partitions changes the
+ * tiling and so the last bits. CSR rows: y^T y, sum y and the count are per-tile sums merged in tile
+ * order and are reproducible; every other entry is added with fp64 vector atomics (columns scatter)
+ * and may differ in its last bits from run to run. Within one result M is symmetric bit for bit.
+ * Errors: PSGD_EINVAL for a null ctx or pointer; PSGD_ESTATE when no partition is registered. A
+ * registry of empty partitions gives zeros.
+ * The calls only read the rows (any kind of registration). Like the scoring calls they wait for
+ * registration copies in flight, order themselves against an epoch running on another stream, use
+ * scratch of their own (psgd_gramian_plan tells how much) and leave the epoch state alone. The
+ * host-pointer form runs on the context's stream and returns when `out` is written; the _device
+ * form takes a device pointer and a stream (NULL: the context's) and is enqueued without a host
+ * synchronisation (the CSR form accumulates in d_out itself). */
+#define PSGD_GRAMIAN_MAX_D 4096
+int32_t psgd_gramian(psgd_ctx* ctx, double* out);
+int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream);
+
+/* How psgd_gramian runs rows of `layout` (0 dense, 1 CSR), `storage` (psgd_dtype) and d features
+ * cut into total_tiles tiles of the statistics passes (the sum over the partitions of
+ * ceil(rows / tile rows)): host code, no device and no context. out[PSGD_GRAM_PLAN_LEN] receives
+ *   [0] the path: 0 dense MFMA, 1 CSR atomics;
+ *   [1] a = d + 2; [2] M's blocks of 16 columns, ceil(a / 16);
+ *   [3] gr, [4] gc: a dense tile group is a rectangle of gr x gc blocks, one wave's accumulators
+ *       (0 for CSR). Group row R keeps the groups from group column floor(R gr / gc) on: the ones
+ *       that meet the upper triangle;
+ *   [5] the number of kept groups;
+ *   [6] tiles a row span, [7] the number of spans: a dense work item is (span, kept group); for CSR
+ *       the two levels in which the tiles' scalar sums are merged;
+ *   [8] bytes of scratch;
+ *   [9] rows of a tile.
+ * Errors: PSGD_EINVAL for a null out, an unknown layout or storage, d <= 0 or total_tiles < 0;
+ * PSGD_EUNSUPPORTED for d > PSGD_GRAMIAN_MAX_D. */
+#define PSGD_GRAM_PLAN_LEN 10
+int32_t psgd_gramian_plan(int32_t layout, int32_t storage, int32_t d, int64_t total_tiles, int64_t* out);
+
 /* One GradientDescent update from a psgd_gradient_sum result `sum` (d + 2 doubles):
  *   (w_out, *regval_out) = updater.compute(w, sum[0 .. d) / sum[d + 1], step_size, iteration, reg_param)
  * for the stateless updaters, MLlib's SimpleUpdater / SquaredL2Updater / L1Updater, with

@@ -22,6 +22,7 @@ from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdate
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
 from .split import kFold, randomSplit
+from .stat import Gramian, corr, covariance, gramian, normal_equations
 from .util import loadLibSVMFile
 
 __all__ = [
@@ -29,6 +30,7 @@ __all__ = [
     "BinaryClassificationMetrics", "MulticlassMetrics", "randomSplit", "kFold",
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "gradient_sum_multinomial", "runMiniBatchSGDMultinomial",
+    "Gramian", "gramian", "covariance", "corr", "normal_equations",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",
     "SGDUpdater", "SimpleSGDUpdater", "SquaredL2SGDUpdater", "L1SGDUpdater",

@@ -33,6 +33,7 @@ EXPORTED = (
     "psgd_column_stats", "psgd_column_stats_device", "psgd_transform_columns", "psgd_transform_columns_device",
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
     "psgd_gradient_sum_multinomial", "psgd_gradient_sum_multinomial_device", "psgd_gradient_multinomial_plan",
+    "psgd_gramian", "psgd_gramian_device", "psgd_gramian_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
     "psgd_evaluate_multinomial", "psgd_evaluate_multinomial_device",
@@ -143,6 +144,9 @@ def lib():
             "psgd_gradient_sum_multinomial": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp], C.c_int32),
             "psgd_gradient_sum_multinomial_device": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp, vp], C.c_int32),
             "psgd_gradient_multinomial_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
+            "psgd_gramian": ([vp, vp], C.c_int32),
+            "psgd_gramian_device": ([vp, vp, vp], C.c_int32),
+            "psgd_gramian_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
             "psgd_gd_update": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, dp],
                                C.c_int32),
             "psgd_gd_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp,
@@ -239,6 +243,21 @@ def gradient_multinomial_plan(layout: str, storage: str, d: int, num_classes: in
             "acc_group", "col_chunks", "class_chunks", "span", "range")
     plan = {k: int(v) for k, v in zip(keys, out)}
     plan["path"] = MN_GRAD_PATHS[plan["path"]]
+    return plan
+
+
+GRAMIAN_MAX_D = 4096   # PSGD_GRAMIAN_MAX_D
+
+
+def gramian_plan(layout: str, storage: str, d: int, total_tiles: int) -> dict:
+    """How psgd_gramian runs rows of `layout` ("dense" / "csr") stored as `storage` ("f32" / "f64")
+    with d features cut into total_tiles tiles (psgd_gramian_plan: host code, no device)."""
+    out = (C.c_int64 * 10)()
+    check(lib().psgd_gramian_plan({"dense": 0, "csr": 1}[layout], {"f64": 0, "f32": 1}[storage], int(d),
+                                  int(total_tiles), out))
+    keys = ("path", "a", "blocks", "gr", "gc", "groups", "span_tiles", "spans", "scratch_bytes", "tile_rows")
+    plan = {k: int(v) for k, v in zip(keys, out)}
+    plan["path"] = ("dense_mfma", "csr")[plan["path"]]
     return plan
 
 
@@ -509,6 +528,19 @@ class Context:
     def column_stats_device(self, out_ptr, stream=None):
         """psgd_column_stats_device: enqueued on `stream`; out[1 + 5 d] on the device."""
         check(self._L.psgd_column_stats_device(self.handle, out_ptr, stream))
+
+    # the augmented Gramian ----------------------------------------------------------------------
+    def gramian(self, d: int):
+        """Host-pointer form (psgd_gramian): M = sum z z^T, z = [x, y, 1], as a (d + 2, d + 2) array."""
+        import numpy as np
+        a = int(d) + 2
+        out = np.zeros((a, a), dtype=np.float64)
+        check(self._L.psgd_gramian(self.handle, out.ctypes.data))
+        return out
+
+    def gramian_device(self, out_ptr, stream=None):
+        """psgd_gramian_device: enqueued on `stream`; out[(d + 2)^2] on the device."""
+        check(self._L.psgd_gramian_device(self.handle, out_ptr, stream))
 
     def transform_columns(self, shift, factor):
         """Host-pointer form (psgd_transform_columns): x = ((double)x - shift) * factor in place on

@@ -458,6 +458,9 @@ struct psgd_ctx {
     // the tile records with the two-pass path's multipliers and the update's block sums, and the
     // host-pointer forms' staging
     DevBuf gdescs, grows, gys, gxstate, grec, gio;
+    // the augmented Gramian (psgd_gramian): the dense items' records / the CSR tiles' scalar sums,
+    // and the host-pointer form's staging of M
+    DevBuf qrec, qio;
     // binary classification metrics (psgd_binary_counts*): the sort's pair buffers and tile tables
     // (with a table of the call's own and the model forms' margins), and the host-pointer forms' staging
     DevBuf mscratch, mio;
@@ -837,6 +840,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->eparts, &ctx->etiles, &ctx->epart, &ctx->ew, &ctx->emargins,
                           &ctx->stile0, &ctx->srec, &ctx->sio,
                           &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
+                          &ctx->qrec, &ctx->qio,
                           &ctx->mscratch, &ctx->mio, &ctx->cidx, &ctx->csel, &ctx->stab,
                           &ctx->watchdog})
             b->release();
@@ -2514,6 +2518,88 @@ int32_t psgd_gradient_multinomial_plan(int32_t layout, int32_t storage, int32_t 
                                                        storage == PSGD_F32 ? 1 : 0, d, num_classes, max_nnz);
     const int32_t v[PSGD_MN_PLAN_LEN] = {gm.path, gm.group,   gm.wlds,       gm.wide,         gm.tile_rows, gm.nvl,
                                          gm.cp,   gm.agroup,  gm.n_colchunks, gm.n_classchunks, gm.span,      gm.range};
+    std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
+// ---- The augmented Gramian (kernels in psgd_gram.hip) ----
+// The same place in the context as the statistics calls: score_prepare, scratch of its own, no epoch
+// state touched.
+static int32_t gramian_width(int32_t d) {
+    if (d > PSGD_GRAMIAN_MAX_D)
+        return fail(PSGD_EUNSUPPORTED, "the Gramian of d = " + std::to_string(d) + " features exceeds the built maximum of " +
+                                           std::to_string(PSGD_GRAMIAN_MAX_D) + " features");
+    return PSGD_OK;
+}
+
+int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_out) return fail(PSGD_EINVAL, "d_out is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const Part& first = ctx->parts.begin()->second;
+    int32_t rc = gramian_width(first.d);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const int P = (int)ctx->parts.size();
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    int64_t max_nnz = 0;
+    for (auto& kv : ctx->parts) max_nnz = std::max(max_nnz, kv.second.max_nnz);
+    const int64_t n_tiles = ctx->stat_tile0.back();
+    const psgd::GramGeom gm = psgd::gram_geometry(first.layout, storage, first.d, n_tiles, max_nnz);
+    HIP_TRY(ctx->qrec.ensure((size_t)gm.scratch_bytes + sizeof(double)));
+    const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>();
+    const int e = first.layout == psgd::kCsr
+                      ? psgd::launch_gramian_csr(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage,
+                                                 ctx->qrec.as<double>(), d_out, ctx->num_cus, st)
+                      : psgd::launch_gramian_dense(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage,
+                                                   ctx->qrec.as<double>(), d_out, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("Gramian launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_gramian(psgd_ctx* ctx, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    size_t len = 0;
+    double* d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        const int32_t d = ctx->parts.begin()->second.d;
+        int32_t rc = gramian_width(d);
+        if (rc) return rc;
+        len = ((size_t)d + 2) * ((size_t)d + 2);
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->qio.ensure(len * sizeof(double)));
+        d_out = ctx->qio.as<double>();
+    }
+    int32_t rc = psgd_gramian_device(ctx, d_out, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(out, d_out, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_gramian_plan(int32_t layout, int32_t storage, int32_t d, int64_t total_tiles, int64_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (layout != psgd::kDense && layout != psgd::kCsr) return fail(PSGD_EINVAL, "unknown layout " + std::to_string(layout));
+    if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
+    if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
+    if (total_tiles < 0) return fail(PSGD_EINVAL, "total_tiles must be >= 0");
+    const int32_t rc = gramian_width(d);
+    if (rc) return rc;
+    const psgd::GramGeom gm = psgd::gram_geometry(layout, storage == PSGD_F32 ? 1 : 0, d, total_tiles, 0);
+    const int64_t v[PSGD_GRAM_PLAN_LEN] = {gm.path, gm.a,   gm.nb,      gm.gr,            gm.gc,
+                                           gm.n_groups, gm.span, gm.n_spans, gm.scratch_bytes, gm.tile_rows};
     std::memcpy(out, v, sizeof v);
     return PSGD_OK;
 }

@@ -340,6 +340,31 @@ int launch_gradient_mn(const ChainDesc* descs, const int64_t* tile0, int n_parts
                        const MnGradGeom& gm, int storage, const double* w, double* scratch, double* out,
                        int num_cus, hipStream_t st);
 
+// ---- The augmented Gramian (psgd_gram.hip: psgd_gramian) ----
+// The plan of a call: host code, no device (psgd_gramian_plan reports it). The tiling is the
+// statistics passes'. Dense: M's blocks of 16 columns are cut into rectangles of gr x gc blocks
+// (nrg x ncg of them); group row R keeps the rectangles from column group R gr / gc on, the ones that
+// meet the upper triangle. An item is (span of `span` consecutive tiles, kept group).
+struct GramGeom {
+    int32_t d, a, nb;        // features, a = d + 2, blocks ceil(a / 16)
+    int32_t path;            // 0 dense MFMA, 1 CSR
+    int32_t gr, gc;          // dense: blocks a group is high and wide (1 x 1, 1 x 2, 2 x 4, 4 x 8)
+    int32_t nrg, ncg;        // dense: group rows and columns
+    int32_t n_groups;        // dense: kept groups
+    int32_t group;           // CSR: lanes across a row's entries (16, 32, 64 by the longest row + 2)
+    int32_t tile_rows;
+    int64_t span, n_spans;   // dense: tiles a span, spans; CSR: the merge of the tiles' scalars
+    int64_t scratch_bytes;
+};
+GramGeom gram_geometry(int layout, int storage, int d, int64_t n_tiles, int64_t max_nnz);
+int gram_groups(int nb, int gr, int gc);
+// out[a * a] = M over the rows of descs[0 .. n_parts); rec is gm.scratch_bytes of scratch. Dense: no
+// floating-point atomics, reproducible bits. CSR: out is the accumulator of fp64 atomics.
+int launch_gramian_dense(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
+                         const GramGeom& gm, int storage, double* rec, double* out, hipStream_t st);
+int launch_gramian_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
+                       const GramGeom& gm, int storage, double* rec, double* out, int num_cus, hipStream_t st);
+
 // w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
 // the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
 int64_t gd_update_blocks(int d);
@@ -418,3 +443,7 @@ int launch_gather_csr(const ChainDesc* descs, const SplitPart* tab, int n_parts,
 // conv, sk, lds_k, tail, lds_bytes, R, MB, D, GS, weights_in, after, setup, wnsq0, zbuf, vec,
 // vec_stride, walpha, wnsq0_buf, reroll_head}. Returns 0, or -1 when an array is null or short.
 extern "C" int32_t psgd_plan_chains(const int64_t* spec, int32_t n_spec, int64_t* plan, int32_t n_plan);
+// The issue rate of v_mfma_f64_16x16x4_f64, for tools/gram_bench.py (not part of the public ABI):
+// `blocks` workgroups of 4 waves, each wave `iters` rounds of `chains` (1, 2, 4, 8) independent MFMAs,
+// enqueued on `stream`. d_out: one double, never written. Returns 0, -1 for bad arguments, or hipError_t.
+extern "C" int32_t psgd_gram_mfma_rate(int32_t blocks, int32_t chains, int32_t iters, double* d_out, void* stream);

@@ -721,18 +721,35 @@ class HipEngine(ShardedEngine):
                                lambda w_ptr, out: self.ctx.gradient_sum_multinomial_device(
                                    K, w_ptr, miniBatchFraction, iteration, out, self.stream.cuda_stream))
 
+    # the augmented Gramian (psgd_gramian_device) ------------------------------------------------
+    def gramian(self):
+        """M = sum_i z_i z_i^T with z_i = [x_i, y_i, 1] over every row of the data, on all ranks, as a
+        device tensor of (d + 2)^2 doubles, row-major (include/psgd.h has the semantics; stat.Gramian
+        reads it). Each rank runs its partitions; the ranks all-gather their matrices (the backends of
+        exchange()) and every rank adds them in rank order (merge_gradient_sums: a loop, not a tree),
+        so all ranks hold the same bits; a rank without partitions contributes zeros."""
+        nf = self._data.num_features
+        if nf > N.GRAMIAN_MAX_D:
+            raise N.IllegalArgumentException(
+                f"requirement failed: the Gramian takes at most {N.GRAMIAN_MAX_D} features (got {nf})")
+        return self._batch_sum((nf + 2) * (nf + 2), None, None,
+                               lambda _w, out: self.ctx.gramian_device(out, self.stream.cuda_stream))
+
     def _batch_sum(self, width: int, to_device, w, call):
+        """call(w_ptr, out_ptr) over this rank's partitions into `width` zeroed doubles, then the ranks'
+        all-gather and the rank-order sum. to_device(w) puts the weights on the device; None for a pass
+        that takes no weights (w_ptr is then None)."""
         torch = self.torch
         caller = torch.cuda.current_stream(self.dev)
         self.stream.wait_stream(caller)
         with torch.cuda.stream(self.stream):
-            w_dev = to_device(w)
+            w_dev = to_device(w) if to_device is not None else None
             buf = torch.zeros(width, dtype=torch.float64, device=self.dev)
             if self.n_local > 0:
                 with self.ctx.engine_lock:
                     if self.ctx.registered_token != self._key:
                         self._register(self._data)
-                    call(w_dev.data_ptr(), buf.data_ptr())
+                    call(None if w_dev is None else w_dev.data_ptr(), buf.data_ptr())
             if self.world > 1:
                 import torch.distributed as dist
                 out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
