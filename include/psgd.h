@@ -433,6 +433,57 @@ int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream);
 #define PSGD_GRAM_PLAN_LEN 10
 int32_t psgd_gramian_plan(int32_t layout, int32_t storage, int32_t d, int64_t total_tiles, int64_t* out);
 
+/* The row projection Y = X B over every registered row -- the pass behind MLlib 1.6.1's
+ * RowMatrix.multiply and PCAModel.transform. B is d * k doubles, row-major (1 <= k <=
+ * PSGD_PROJECT_MAX_K); Y[r][j] = sum_i x[r][i] B[i][j] with the stored values widened to double and
+ * every product added with fma, all in fp64 whatever the storage. A CSR row's absent entries are
+ * zeros. The pad columns of a zero-copy row (ld > d) never reach the arithmetic.
+ * psgd_project_device writes every partition at once: d_y_out[c] / d_labels_out[c] (host arrays of
+ * device pointers, one per registered partition in partition-index order, as for
+ * psgd_gather_dense_device; null allowed where a partition is empty) receive partition c's rows, in
+ * order, as dense rows of out_storage (psgd_dtype: the fp64 result rounded once) at the pitch
+ * ld_out elements -- ld_out >= k, rows 16-byte aligned (ld_out * sizeof(out_storage) % 16 == 0 and
+ * the pointers too), columns [k, ld_out) written as zeros -- and its labels, bit for bit. That is
+ * psgd_register_dense_device's contract: the result can be registered zero-copy at once.
+ * psgd_project writes partition `part` alone to host memory: out receives n_rows * k doubles, the
+ * bytes of the f64 device form without its pad.
+ * Reproducibility: no atomics. Dense rows go through v_mfma_f64_16x16x4_f64 (M = rows, K = features,
+ * N = components), each output one chain along the features in an order fixed by (d, k, storage);
+ * CSR rows add in entry order. Every output has the same bits from call to call.
+ * Errors: PSGD_EINVAL for a null ctx or pointer (a null table entry of a non-empty partition
+ * included), k < 1, an unknown out_storage or a bad ld_out; PSGD_EUNSUPPORTED for k >
+ * PSGD_PROJECT_MAX_K; PSGD_ESTATE when no partition is registered or `part` is not. A registry of
+ * empty partitions writes nothing.
+ * The calls only read the rows (any kind of registration). Like the scoring calls they wait for
+ * registration copies in flight, order themselves against an epoch running on another stream, use
+ * scratch of their own (psgd_project_plan tells how much) and leave the epoch state alone. The
+ * _device form takes device pointers and a stream (NULL: the context's); it waits once for its
+ * pointer table to leave the host. */
+#define PSGD_PROJECT_MAX_K 256
+int32_t psgd_project_device(psgd_ctx* ctx, int32_t k, const double* d_B, int32_t out_storage, int64_t ld_out,
+                            void* const* d_y_out, double* const* d_labels_out, void* stream);
+int32_t psgd_project(psgd_ctx* ctx, int64_t part, int32_t k, const double* B, double* out);
+
+/* How psgd_project runs rows of `layout` (0 dense, 1 CSR), `storage` (psgd_dtype) and d features
+ * against k components (max_nnz: the longest CSR row; it changes no decision today): host code, no
+ * device and no context. out[PSGD_PROJECT_PLAN_LEN] receives
+ *   [0] the path: 0 dense MFMA with B in LDS, 1 dense MFMA with B read through L2, 2 CSR with B in
+ *       LDS, 3 CSR with B read through L2. B lives in LDS while d (dense: rounded up to [4]) x kpad
+ *       doubles fit a CU's 160 KiB;
+ *   [1] kpad = 16 ceil(k / 16), the columns of the widened B;
+ *   [2] rows a wave takes at a time: the 16 rows of an MFMA; CSR 64 / the lanes a row;
+ *   [3] dense: component blocks of 16 a wave keeps in registers (1, 2, 4: k > 64 reads the rows once a
+ *       chunk of 4 blocks); CSR: components a lane keeps;
+ *   [4] dense: the feature chunk, features one 16-byte vector a lane covers across the wave (16 f32,
+ *       8 f64: one vector feeds that many / 4 MFMAs a block); CSR 0;
+ *   [5] bytes of dynamic LDS (0 on the L2 paths);
+ *   [6] bytes of scratch (dense: B in the MFMA operands' order);
+ *   [7] CSR: lanes a row, the power of two >= k, 64 at most (dense 0).
+ * Errors: PSGD_EINVAL for a null out, an unknown layout or storage, d <= 0, k < 1 or max_nnz < 0;
+ * PSGD_EUNSUPPORTED for k > PSGD_PROJECT_MAX_K. */
+#define PSGD_PROJECT_PLAN_LEN 8
+int32_t psgd_project_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t max_nnz, int64_t* out);
+
 /* One GradientDescent update from a psgd_gradient_sum result `sum` (d + 2 doubles):
  *   (w_out, *regval_out) = updater.compute(w, sum[0 .. d) / sum[d + 1], step_size, iteration, reg_param)
  * for the stateless updaters, MLlib's SimpleUpdater / SquaredL2Updater / L1Updater, with

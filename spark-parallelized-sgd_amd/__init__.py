@@ -13,7 +13,7 @@ from ._native import (DeviceError, IllegalArgumentException, UnsupportedOperatio
 from .data import (CsrPartition, DensePartition, DeviceCsrPartition, DevicePartition, PartitionedData,
                    shard_range)
 from .gradient import Gradient, HingeGradient, LeastSquaresGradient, LogisticGradient
-from .feature import StandardScaler, StandardScalerModel, column_stats
+from .feature import PCA, PCAModel, StandardScaler, StandardScalerModel, column_stats
 from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine, ParallelizedSGD, ShardedEngine,
                            evaluate, evaluate_multinomial, make_params, runParallelizedSGD)
 from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradient_sum_multinomial, runMiniBatchSGD,
@@ -22,7 +22,8 @@ from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdate
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
 from .split import kFold, randomSplit
-from .stat import Gramian, corr, covariance, gramian, normal_equations
+from .stat import (Gramian, computePrincipalComponents, computeSVD, corr, covariance, gramian, multiply,
+                   normal_equations)
 from .util import loadLibSVMFile
 
 __all__ = [
@@ -31,6 +32,7 @@ __all__ = [
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "gradient_sum_multinomial", "runMiniBatchSGDMultinomial",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
+    "multiply", "computePrincipalComponents", "computeSVD", "PCA", "PCAModel",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",
     "SGDUpdater", "SimpleSGDUpdater", "SquaredL2SGDUpdater", "L1SGDUpdater",

@@ -34,6 +34,7 @@ EXPORTED = (
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
     "psgd_gradient_sum_multinomial", "psgd_gradient_sum_multinomial_device", "psgd_gradient_multinomial_plan",
     "psgd_gramian", "psgd_gramian_device", "psgd_gramian_plan",
+    "psgd_project", "psgd_project_device", "psgd_project_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
     "psgd_evaluate_multinomial", "psgd_evaluate_multinomial_device",
@@ -147,6 +148,9 @@ def lib():
             "psgd_gramian": ([vp, vp], C.c_int32),
             "psgd_gramian_device": ([vp, vp, vp], C.c_int32),
             "psgd_gramian_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
+            "psgd_project": ([vp, C.c_int64, C.c_int32, vp, vp], C.c_int32),
+            "psgd_project_device": ([vp, C.c_int32, vp, C.c_int32, C.c_int64, vp, vp, vp], C.c_int32),
+            "psgd_project_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
             "psgd_gd_update": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, dp],
                                C.c_int32),
             "psgd_gd_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp,
@@ -247,6 +251,20 @@ def gradient_multinomial_plan(layout: str, storage: str, d: int, num_classes: in
 
 
 GRAMIAN_MAX_D = 4096   # PSGD_GRAMIAN_MAX_D
+PROJECT_MAX_K = 256    # PSGD_PROJECT_MAX_K
+PROJECT_PATHS = ("dense_lds", "dense_l2", "csr_lds", "csr_l2")
+
+
+def project_plan(layout: str, storage: str, d: int, k: int, max_nnz: int = 0) -> dict:
+    """How psgd_project runs rows of `layout` ("dense" / "csr") stored as `storage` ("f32" / "f64")
+    with d features against k components (psgd_project_plan: host code, no device)."""
+    out = (C.c_int64 * 8)()
+    check(lib().psgd_project_plan({"dense": 0, "csr": 1}[layout], {"f64": 0, "f32": 1}[storage], int(d), int(k),
+                                  int(max_nnz), out))
+    keys = ("path", "kpad", "rows_wave", "comp_blocks", "feature_chunk", "lds_bytes", "scratch_bytes", "row_lanes")
+    plan = {k_: int(v) for k_, v in zip(keys, out)}
+    plan["path"] = PROJECT_PATHS[plan["path"]]
+    return plan
 
 
 def gramian_plan(layout: str, storage: str, d: int, total_tiles: int) -> dict:
@@ -541,6 +559,25 @@ class Context:
     def gramian_device(self, out_ptr, stream=None):
         """psgd_gramian_device: enqueued on `stream`; out[(d + 2)^2] on the device."""
         check(self._L.psgd_gramian_device(self.handle, out_ptr, stream))
+
+    # the row projection -------------------------------------------------------------------------
+    def project(self, part: int, n_rows: int, B):
+        """Host-pointer form (psgd_project): partition `part`'s rows times B [d, k] as an (n_rows, k)
+        float64 array."""
+        import numpy as np
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        out = np.zeros((int(n_rows), B.shape[1]), dtype=np.float64)
+        check(self._L.psgd_project(self.handle, int(part), int(B.shape[1]), B.ctypes.data, out.ctypes.data))
+        return out
+
+    def project_device(self, k: int, b_ptr, out_storage: int, ld_out: int, y_ptrs, label_ptrs, stream=None):
+        """psgd_project_device: y_ptrs / label_ptrs the per-partition device addresses (0 where a
+        partition is empty), in partition-index order."""
+        import numpy as np
+        ys = np.ascontiguousarray(y_ptrs, dtype=np.uint64)
+        ls = np.ascontiguousarray(label_ptrs, dtype=np.uint64)
+        check(self._L.psgd_project_device(self.handle, int(k), b_ptr, int(out_storage), int(ld_out), ys.ctypes.data,
+                                          ls.ctypes.data, stream))
 
     def transform_columns(self, shift, factor):
         """Host-pointer form (psgd_transform_columns): x = ((double)x - shift) * factor in place on

@@ -2925,6 +2925,125 @@ int32_t psgd_gather_csr_device(psgd_ctx* ctx, const int32_t* d_rows, const int64
     return PSGD_OK;
 }
 
+// ---- The row projection Y = X B (kernels in psgd_project.hip) ----
+// The same place in the context as the compactions: score_prepare, the table in ctx->stab, B in the
+// MFMA operands' order in ctx->qrec, no epoch state touched.
+static int32_t project_args(int32_t k) {
+    if (k < 1) return fail(PSGD_EINVAL, "k must be at least 1");
+    if (k > PSGD_PROJECT_MAX_K)
+        return fail(PSGD_EUNSUPPORTED, "a projection onto k = " + std::to_string(k) + " components exceeds the built maximum of " +
+                                           std::to_string(PSGD_PROJECT_MAX_K));
+    return PSGD_OK;
+}
+
+// Every partition (only < 0) or partition `only` alone projected on `st` (ctx->mu held, score_prepare
+// done). A partition left out takes no tile; y_out may be null (no labels copied).
+static int32_t project_enqueue(psgd_ctx* ctx, int32_t k, const double* d_B, int32_t out_storage, int64_t ld_out,
+                               void* const* x_out, double* const* y_out, int64_t only, hipStream_t st) {
+    const Part& first = ctx->parts.begin()->second;
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    int64_t max_nnz = 0;
+    for (auto& kv : ctx->parts) max_nnz = std::max(max_nnz, kv.second.max_nnz);
+    const psgd::ProjGeom gm = psgd::project_geometry(first.layout, storage, first.d, k, max_nnz);
+    const size_t P = ctx->parts.size();
+    std::vector<psgd::ProjPart> tab(P + 1);
+    int64_t tiles = 0;
+    size_t c = 0;
+    for (auto& kv : ctx->parts) {
+        const Part& q = kv.second;
+        const bool take = (only < 0 || kv.first == only) && q.n_rows > 0;
+        if (take && (!x_out[c] || (only < 0 && !y_out[c])))
+            return fail(PSGD_EINVAL, "an output pointer of partition " + std::to_string(kv.first) + " is null");
+        if (take && ((uintptr_t)x_out[c] % 16) != 0) return fail(PSGD_EINVAL, "output rows must be 16-byte aligned");
+        tab[c] = psgd::ProjPart{tiles, take ? x_out[c] : nullptr, take && y_out ? y_out[c] : nullptr};
+        if (take) tiles += (q.n_rows + gm.tile_rows - 1) / gm.tile_rows;
+        ++c;
+    }
+    tab[P] = psgd::ProjPart{tiles, nullptr, nullptr};
+    if (tiles == 0) return PSGD_OK;
+    HIP_TRY(ctx->stab.ensure(tab.size() * sizeof(psgd::ProjPart)));
+    HIP_TRY(ctx->qrec.ensure((size_t)gm.scratch_bytes + sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(ctx->stab.p, tab.data(), tab.size() * sizeof(psgd::ProjPart), hipMemcpyHostToDevice, st));
+    // the table leaves a host vector of this call: wait for the copy
+    HIP_TRY(hipStreamSynchronize(st));
+    // (a partition left out keeps its descriptor but owns no tile: the tile search never lands on it)
+    const int e = psgd::launch_project(ctx->descs.as<psgd::ChainDesc>(), ctx->stab.as<psgd::ProjPart>(), (int)P, tiles, gm,
+                                       storage, out_storage == PSGD_F32 ? 1 : 0, d_B, ctx->qrec.as<double>(), ld_out,
+                                       ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("projection launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_project_device(psgd_ctx* ctx, int32_t k, const double* d_B, int32_t out_storage, int64_t ld_out,
+                            void* const* d_y_out, double* const* d_labels_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_B || !d_y_out || !d_labels_out) return fail(PSGD_EINVAL, "d_B/d_y_out/d_labels_out are null");
+    int32_t rc = project_args(k);
+    if (rc) return rc;
+    if (out_storage != PSGD_F64 && out_storage != PSGD_F32)
+        return fail(PSGD_EINVAL, "unknown output storage dtype " + std::to_string(out_storage));
+    if (ld_out < k || ((size_t)ld_out * dtype_size(out_storage)) % 16 != 0)
+        return fail(PSGD_EINVAL, "need ld_out >= k and 16-byte aligned rows (ld_out * sizeof(out_storage) % 16 == 0)");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    return project_enqueue(ctx, k, d_B, out_storage, ld_out, d_y_out, d_labels_out, -1, st);
+}
+
+int32_t psgd_project(psgd_ctx* ctx, int64_t part, int32_t k, const double* B, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!B) return fail(PSGD_EINVAL, "B is null");
+    int32_t rc = project_args(k);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const auto it = ctx->parts.find(part);
+    if (it == ctx->parts.end()) return fail(PSGD_ESTATE, "partition " + std::to_string(part) + " is not registered");
+    const size_t n = (size_t)it->second.n_rows, d = (size_t)it->second.d;
+    if (n == 0) return PSGD_OK;
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    // B, then the rows at an even pitch (16-byte aligned rows of doubles)
+    const size_t ld = ((size_t)k + 1) & ~(size_t)1;
+    const size_t b_len = (d * (size_t)k + 1) & ~(size_t)1;
+    HIP_TRY(ctx->qio.ensure((b_len + n * ld) * sizeof(double)));
+    double* d_B = ctx->qio.as<double>();
+    double* d_y = d_B + b_len;
+    HIP_TRY(hipMemcpyAsync(d_B, B, d * (size_t)k * sizeof(double), hipMemcpyHostToDevice, st));
+    const size_t P = ctx->parts.size();
+    std::vector<void*> xs(P, nullptr);
+    xs[(size_t)std::distance(ctx->parts.begin(), it)] = d_y;
+    rc = project_enqueue(ctx, k, d_B, PSGD_F64, (int64_t)ld, xs.data(), nullptr, part, st);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy2DAsync(out, (size_t)k * sizeof(double), d_y, ld * sizeof(double), (size_t)k * sizeof(double), n,
+                             hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PSGD_OK;
+}
+
+int32_t psgd_project_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t max_nnz, int64_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (layout != psgd::kDense && layout != psgd::kCsr) return fail(PSGD_EINVAL, "unknown layout " + std::to_string(layout));
+    if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
+    if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
+    if (max_nnz < 0) return fail(PSGD_EINVAL, "max_nnz must be >= 0");
+    const int32_t rc = project_args(k);
+    if (rc) return rc;
+    const psgd::ProjGeom gm = psgd::project_geometry(layout, storage == PSGD_F32 ? 1 : 0, d, k, max_nnz);
+    const int64_t v[PSGD_PROJECT_PLAN_LEN] = {gm.path,   gm.kpad,      gm.rows_wave,     gm.cb,
+                                              gm.fchunk, gm.lds_bytes, gm.scratch_bytes, gm.group};
+    std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
 int32_t psgd_sample_partition(int32_t device, int64_t seed, int64_t n, double fraction, int32_t* rows_out,
                               int64_t* m_out) {
     if (!m_out || (n > 0 && !rows_out)) return fail(PSGD_EINVAL, "rows_out/m_out is null");

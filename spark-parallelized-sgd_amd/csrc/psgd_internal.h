@@ -365,6 +365,37 @@ int launch_gramian_dense(const ChainDesc* descs, const int64_t* tile0, int n_par
 int launch_gramian_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
                        const GramGeom& gm, int storage, double* rec, double* out, int num_cus, hipStream_t st);
 
+// ---- The row projection Y = X B (psgd_project.hip: psgd_project) ----
+// The plan of a call: host code, no device (psgd_project_plan reports it).
+enum ProjPath { kProjDenseLds = 0, kProjDenseL2 = 1, kProjCsrLds = 2, kProjCsrL2 = 3 };
+struct ProjGeom {
+    int32_t d, k;
+    int32_t kpad, nb;        // 16 ceil(k / 16) columns of the widened B, its blocks of 16
+    int32_t path;            // ProjPath: where the kernel reads B from
+    int32_t rows_wave;       // dense: the 16 rows of an MFMA; CSR: 64 / group
+    int32_t cb;              // dense: component blocks a wave keeps (1, 2, 4); CSR: components a lane keeps
+    int32_t fchunk;          // dense: features a step of one 16-byte vector a lane covers (16 f32, 8 f64)
+    int32_t dpad;            // dense: d rounded up to whole steps
+    int32_t group;           // CSR: lanes a row (the power of two >= k, at most 64)
+    int32_t tile_rows;       // rows a tile: dense 16, CSR 256
+    int64_t lds_bytes;       // dynamic LDS of the launch (0: B is read through L2)
+    int64_t scratch_bytes;   // dense: B in the MFMA operands' order, dpad x kpad doubles
+};
+ProjGeom project_geometry(int layout, int storage, int d, int k, int64_t max_nnz);
+// One partition of a projection: its rows go to x [n_rows * ld_out] (the output dtype) and its labels
+// to y [n_rows] (nullable: not copied). The source rows are cut into tiles of gm.tile_rows rows,
+// numbered from tile0 on across the partitions in partition-index order; entry n_parts closes the list.
+struct ProjPart {
+    int64_t tile0;
+    void* x;
+    double* y;
+};
+// B [d * k] row-major; Bp gm.scratch_bytes of scratch (dense). storage / out_storage: 0 = f64, 1 = f32.
+// ld_out in elements: >= k, rows 16-byte aligned; columns [k, ld_out) are written as zeros.
+int launch_project(const ChainDesc* descs, const ProjPart* tab, int n_parts, int64_t n_tiles, const ProjGeom& gm,
+                   int storage, int out_storage, const double* B, double* Bp, int64_t ld_out, int num_cus,
+                   hipStream_t st);
+
 // w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
 // the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
 int64_t gd_update_blocks(int d);

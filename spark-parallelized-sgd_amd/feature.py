@@ -11,6 +11,12 @@ Statistics.colStats), on the rows the context already holds in HBM.
 The statistics are one streaming fp64 pass over dense rows (two over CSR rows); the transform is
 applied in place to the context's copy of the rows when an engine registers `scaled`
 (HipEngine._register), so the host arrays are neither copied nor scaled.
+
+  pca = PCA(k).fit(data)                             # mllib.feature.PCA over stat.covariance
+  reduced = pca.transform(data)                      # new device rows of k features, labels kept
+
+PCA is this project's restatement of MLlib 1.6.1's, not pinned to its source; the components' sign
+convention and explainedVariance are stat.Gramian.principal_components'.
 """
 from __future__ import annotations
 
@@ -18,7 +24,7 @@ from typing import Optional
 
 import numpy as np
 
-from ._native import IllegalArgumentException
+from ._native import PROJECT_MAX_K, IllegalArgumentException
 from .data import CsrPartition, DeviceCsrPartition, DevicePartition, PartitionedData
 
 
@@ -110,3 +116,51 @@ class StandardScaler:
     def fit(self, data: PartitionedData, *, engine=None) -> StandardScalerModel:
         stats = column_stats(data, engine=engine)
         return StandardScalerModel(np.sqrt(stats.variance), stats.mean, self.withStd, self.withMean)
+
+
+class PCAModel:
+    """MLlib PCAModel(k, pc): transform multiplies the rows by pc (d x k). As in MLlib it does not
+    centre them. explainedVariance is MLlib 2.0's member."""
+
+    def __init__(self, k, pc, explainedVariance=None):
+        self.pc = np.ascontiguousarray(pc, dtype=np.float64)
+        if self.pc.ndim != 2 or isinstance(k, bool) or int(k) != self.pc.shape[1]:
+            raise IllegalArgumentException(
+                f"requirement failed: pc must be [d, k] with k = {k} columns (got shape {self.pc.shape})")
+        self.k = int(k)
+        if not 1 <= self.k <= PROJECT_MAX_K:
+            raise IllegalArgumentException(
+                f"requirement failed: PCA takes 1 <= k <= {PROJECT_MAX_K} components (got {self.k})")
+        self.explainedVariance = (None if explainedVariance is None
+                                  else np.ascontiguousarray(explainedVariance, dtype=np.float64))
+
+    def transform(self, data: PartitionedData, storage=None, *, engine=None) -> PartitionedData:
+        """stat.multiply(data, pc): new dense device rows of k features with the rows' labels. A source
+        column_transform is in the rows and is not carried over."""
+        if self.pc.shape[0] != data.num_features:
+            raise IllegalArgumentException(
+                f"requirement failed: vector sizes do not match: Expected {self.pc.shape[0]} but found "
+                f"{data.num_features}")
+        from .stat import multiply
+        return multiply(data, self.pc, storage, engine=engine)
+
+
+class PCA:
+    """MLlib 1.6.1 feature.PCA(k): fit computes the covariance on the device
+    (stat.computePrincipalComponents) and returns the model of the top k components."""
+
+    def __init__(self, k):
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or int(k) < 1:
+            raise IllegalArgumentException(f"requirement failed: PCA requires a whole number of components k >= 1 (got {k!r})")
+        if int(k) > PROJECT_MAX_K:
+            raise IllegalArgumentException(
+                f"requirement failed: PCA takes at most {PROJECT_MAX_K} components (got {k})")
+        self.k = int(k)
+
+    def fit(self, data: PartitionedData, *, engine=None) -> PCAModel:
+        if self.k > data.num_features:
+            raise IllegalArgumentException(
+                f"requirement failed: source vector size is {data.num_features} must be greater than k={self.k}")
+        from .stat import computePrincipalComponents
+        pc, explained = computePrincipalComponents(data, self.k, engine=engine)
+        return PCAModel(self.k, pc, explained)

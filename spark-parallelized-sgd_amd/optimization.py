@@ -903,6 +903,69 @@ class HipEngine(ShardedEngine):
         out.partition_counts = part_counts
         return out
 
+    # the row projection (psgd_project_device; stat.multiply, feature.PCAModel) ---------------------
+    def project(self, B, storage=None) -> PartitionedData:
+        """Y = X B for B [d, k] (a numpy array or a device tensor), as a PartitionedData of dense device
+        partitions of k features built the way split_cell builds its result: one arena, this rank's
+        block filled by one launch over all its partitions (partition p holds the rows of source
+        partition p in order, with their labels), empty placeholders for the other ranks' partitions,
+        and `partition_counts`, every partition's row count on every rank. storage ("f32" / "f64" or a
+        torch dtype; None keeps the source's) is the result's dtype: the fp64 product rounded once.
+        The rows come from the context's registered copy: a source column_transform is in them, the
+        result carries none."""
+        torch = self.torch
+        data, P, d = self._data, self._data.num_partitions, self._data.num_features
+        if torch.is_tensor(B):
+            _require(B.dim() == 2 and B.shape[0] == d, f"B must be [{d}, k] (got {tuple(B.shape)})")
+        else:
+            B = np.asarray(B, dtype=np.float64)
+            _require(B.ndim == 2 and B.shape[0] == d, f"B must be [{d}, k] (got {B.shape})")
+        k = int(B.shape[1])
+        _require(1 <= k <= N.PROJECT_MAX_K, f"a projection takes 1 <= k <= {N.PROJECT_MAX_K} components (got {k})")
+        if storage is None:
+            odt = self._storage_dtype()
+        else:
+            odt = {"f32": torch.float32, "f64": torch.float64, torch.float32: torch.float32,
+                   torch.float64: torch.float64}.get(storage)
+            _require(odt is not None, f"storage must be 'f32', 'f64' or None (got {storage!r})")
+        n_rows = np.array([data.partitions[p].n_rows for p in range(self.lo, self.hi)], dtype=np.int64)
+        m0 = np.concatenate([[0], np.cumsum(n_rows, dtype=np.int64)]).astype(np.int64)
+        M = int(m0[-1])
+        vec = 4 if odt == torch.float32 else 2
+        ld = (k + vec - 1) // vec * vec
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            if torch.is_tensor(B):
+                b_dev = B.to(device=self.dev, dtype=torch.float64).contiguous()
+            else:
+                b_dev = torch.from_numpy(np.ascontiguousarray(B)).to(self.dev)
+            y = torch.empty(M, dtype=torch.float64, device=self.dev)
+            Y = torch.empty((M, ld), dtype=odt, device=self.dev)
+            ys = [y[int(m0[i]): int(m0[i + 1])] for i in range(self.n_local)]
+            xs = [Y[int(m0[i]): int(m0[i + 1])] for i in range(self.n_local)]
+            if M > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    ptr = lambda ts: [t.data_ptr() if t.numel() else 0 for t in ts]
+                    self.ctx.project_device(k, b_dev.data_ptr(), N.F32 if odt == torch.float32 else N.F64, ld,
+                                            ptr(xs), ptr(ys), self.stream.cuda_stream)
+            keep = torch.cuda.Event()
+            keep.record(self.stream)
+        caller.wait_stream(self.stream)
+        for t in (y, Y):
+            t.record_stream(caller)
+        keep.synchronize()   # b_dev may be a temporary of this call
+        local = [DevicePartition(ys[i], xs[i], k) for i in range(self.n_local)]
+        empty = lambda: DevicePartition(y[:0], Y[:0], k)
+        part_counts = getattr(data, "partition_counts", None)
+        if part_counts is None:
+            part_counts = np.array([q.n_rows for q in data.partitions], dtype=np.int64)
+        out = PartitionedData([empty() for _ in range(self.lo)] + local + [empty() for _ in range(P - self.hi)])
+        out.partition_counts = np.array(part_counts, dtype=np.int64)
+        return out
+
 
 def merge_gradient_sums(rows):
     """Rows of {gradientSum[d], lossSum, count}, one a rank, added in row order: ((r0 + r1) + r2) + ..

@@ -6,21 +6,55 @@ follows from it on the host -- RowMatrix.computeGramianMatrix / computeCovarianc
   g.gram, g.xty, g.yty               # X^T X, X^T y, y^T y
   g.covariance(), g.corr()           # computeCovariance, Statistics.corr(., "pearson")
   w_star = g.normal_equations(regParam=0.1)
+  pc, explained = g.principal_components(k)   # RowMatrix.computePrincipalComponents
+  s, V = g.svd(k)                             # RowMatrix.computeSVD, local-eigs mode
+  projected = multiply(data, pc)              # RowMatrix.multiply: new rows on the device
 
 w_star is the point every run of ParallelizedSGD / GradientDescent with LeastSquaresGradient and
 SquaredL2SGDUpdater converges toward. The pass is fp64 on the device (fp64 MFMA over dense rows, fp64
 atomics over CSR rows; include/psgd.h has the semantics); everything after it is numpy fp64 on the
-host over a (d + 2) x (d + 2) array, so `Gramian` can be built from any such array.
+host over a (d + 2) x (d + 2) array, so `Gramian` can be built from any such array. `multiply` is
+the one function here that writes rows: Y = X B on the device (fp64 MFMA over dense rows,
+HipEngine.project), the rows' labels kept beside them.
 
 The definitions are this project's restatement of MLlib 1.6.1 (RowMatrix.computeCovariance,
-PearsonCorrelation), not pinned to its source.
+PearsonCorrelation, RowMatrix.multiply / computePrincipalComponents / computeSVD), not pinned to its
+source. Two things are this project's own: the sign of a principal component or singular vector is
+fixed so that its largest-magnitude entry is positive (MLlib leaves it to LAPACK), and
+explainedVariance is MLlib 2.0's member (1.6.1 returns the components alone).
 """
 from __future__ import annotations
 
 import numpy as np
 
-from ._native import IllegalArgumentException
+from ._native import PROJECT_MAX_K, IllegalArgumentException
 from .data import PartitionedData
+
+
+def _check_k(k, d: int, what: str) -> int:
+    """1 <= k <= d, a whole number (bool and float are refused)."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)):
+        raise IllegalArgumentException(f"requirement failed: {what} takes a whole number k (got {k!r})")
+    if not 1 <= int(k) <= d:
+        raise IllegalArgumentException(f"requirement failed: {what} needs 1 <= k <= {d} (got {k})")
+    return int(k)
+
+
+def _fix_signs(V: np.ndarray) -> np.ndarray:
+    """Each column's largest-magnitude entry (the first of equals) made positive."""
+    V = np.array(V, dtype=np.float64)
+    top = np.argmax(np.abs(V), axis=0)
+    neg = V[top, np.arange(V.shape[1])] < 0.0
+    V[:, neg] = -V[:, neg]
+    return V
+
+
+def _eigh_desc(A: np.ndarray):
+    """Eigenvalues in descending order with their eigenvectors as columns, signs fixed (numpy fp64)."""
+    A = 0.5 * (A + A.T)
+    w, V = np.linalg.eigh(A)
+    order = np.argsort(-w, kind="stable")
+    return w[order], _fix_signs(V[:, order])
 
 
 class Gramian:
@@ -115,6 +149,39 @@ class Gramian:
                 "columns): use regParam > 0 or drop the dependent columns") from None
         return np.linalg.solve(L.T, np.linalg.solve(L, b))
 
+    def principal_components(self, k):
+        """RowMatrix.computePrincipalComponents(k): (pc, explainedVariance) from the
+        eigen-decomposition of covariance() in numpy fp64. pc is d x k, its columns the eigenvectors
+        in descending eigenvalue order, each with its largest-magnitude entry positive (this project's
+        convention; MLlib leaves the sign to LAPACK); explainedVariance[j] is eigenvalue j over the
+        trace (MLlib 2.0's member). Needs 1 <= k <= d and at least 2 rows."""
+        k = _check_k(k, self.d, "computePrincipalComponents")
+        w, V = _eigh_desc(self.covariance())
+        total = float(np.sum(w))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            explained = w / total
+        return np.ascontiguousarray(V[:, :k]), explained[:k].copy()
+
+    def svd(self, k, rCond: float = 1e-9):
+        """RowMatrix.computeSVD(k, rCond = rCond) in its local-eigs mode: (s, V) with s the square roots
+        of the leading eigenvalues of X^T X, descending, and V (d x len(s)) their eigenvectors (signs as
+        in principal_components). Only sigma > rCond * sigma_0 are kept: fewer than k may be returned.
+        An eigenvalue at or below the fp64 eigen-solver's noise floor, d * 2^-52 * sigma_0^2 (the
+        tolerance of numpy.linalg.matrix_rank), counts as zero whatever rCond is: the square root of
+        such noise is about 1e-8 sigma_0 and would pass rCond = 1e-9 as a singular value."""
+        k = _check_k(k, self.d, "computeSVD")
+        if not 0.0 <= float(rCond) <= 1.0:
+            raise IllegalArgumentException(f"requirement failed: rCond must be within [0, 1] but got {rCond}")
+        w, V = _eigh_desc(self.gram)
+        w = np.where(w > self.d * np.finfo(np.float64).eps * w[0], w, 0.0)
+        sigma = np.sqrt(np.maximum(w, 0.0))
+        if not sigma[0] > 0.0:
+            raise IllegalArgumentException("requirement failed: computeSVD needs a matrix with a non-zero entry")
+        keep = 0
+        while keep < k and sigma[keep] > float(rCond) * sigma[0]:
+            keep += 1
+        return sigma[:keep].copy(), np.ascontiguousarray(V[:, :keep])
+
     def __repr__(self) -> str:
         return f"Gramian(d={self.d}, count={self.count})"
 
@@ -151,3 +218,42 @@ def normal_equations(data: PartitionedData, regParam: float = 0.0, *, engine=Non
     if not float(regParam) >= 0.0:
         raise IllegalArgumentException(f"requirement failed: regParam must be nonnegative but got {regParam}")
     return gramian(data, engine=engine).normal_equations(regParam)
+
+
+def multiply(data: PartitionedData, B, storage=None, *, engine=None) -> PartitionedData:
+    """RowMatrix.multiply(B) keeping the labels: the rows of `data` times B [d, k] (a numpy array or a
+    device tensor) as a new PartitionedData of dense device partitions of k features, partition p
+    the rows of source partition p in order (HipEngine.project; include/psgd.h has the semantics).
+    storage ("f32" / "f64"; None keeps the source's) is the result's dtype."""
+    shape = tuple(getattr(B, "shape", ())) or np.shape(B)
+    if len(shape) != 2 or shape[0] != data.num_features:
+        raise IllegalArgumentException(
+            f"requirement failed: B must be [{data.num_features}, k] to multiply rows of {data.num_features} "
+            f"features (got shape {tuple(shape)})")
+    if not 1 <= shape[1] <= PROJECT_MAX_K:
+        raise IllegalArgumentException(
+            f"requirement failed: multiply takes 1 <= k <= {PROJECT_MAX_K} columns (got {shape[1]})")
+    if storage not in (None, "f32", "f64"):
+        raise IllegalArgumentException(f"requirement failed: storage must be 'f32', 'f64' or None (got {storage!r})")
+    if engine is None:
+        from .optimization import HipEngine, _dist
+        rank, world, _ = _dist()
+        engine = HipEngine(data, rank, world)
+    return engine.project(B, storage)
+
+
+def computePrincipalComponents(data: PartitionedData, k, *, engine=None):
+    """RowMatrix.computePrincipalComponentsAndExplainedVariance(k) over the rows of `data`:
+    Gramian.principal_components of one device pass."""
+    _check_k(k, data.num_features, "computePrincipalComponents")
+    return gramian(data, engine=engine).principal_components(k)
+
+
+def computeSVD(data: PartitionedData, k, computeU: bool = False, rCond: float = 1e-9, *, engine=None):
+    """RowMatrix.computeSVD(k, computeU, rCond), local-eigs mode only: (U, s, V) with U = None unless
+    computeU, else the rows X V diag(1 / s) as multiply returns them (f64 whatever the source's storage:
+    its columns are orthonormal to fp64 only there)."""
+    _check_k(k, data.num_features, "computeSVD")
+    s, V = gramian(data, engine=engine).svd(k, rCond)
+    U = multiply(data, V / s[None, :], "f64", engine=engine) if computeU else None
+    return U, s, V
