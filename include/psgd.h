@@ -433,6 +433,46 @@ int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream);
 #define PSGD_GRAM_PLAN_LEN 10
 int32_t psgd_gramian_plan(int32_t layout, int32_t storage, int32_t d, int64_t total_tiles, int64_t* out);
 
+/* The number of registered rows: the length of the per-row arrays below. Their order is local row
+ * order: the registered partitions in partition-index order, a partition's rows in iterator order.
+ * Errors: PSGD_EINVAL for a null ctx or out. */
+int32_t psgd_local_rows(psgd_ctx* ctx, int64_t* out);
+
+/* The row-weighted Gramian M_w = sum_i omega_i z_i z_i^T over every registered row, omega one double per
+ * row in local row order (psgd_local_rows of them). The layout is M's:
+ *   X^T W X = M[0..d, 0..d),  X^T W y = M[0..d, d],  sum w y^2 = M[d][d],
+ *   X^T W 1 = M[0..d, d + 1],  sum w y = M[d][d + 1],  sum w = M[d + 1][d + 1].
+ * With omega the loss's curvature at the current weights (psgd_row_curvature) M_w[0..d, 0..d) is the
+ * Hessian of the loss sum; with instance weights it is the moment matrix of weighted least squares.
+ * Any finite omega is in contract, 0 and negative values included; NaN and Inf are outside it.
+ * Dense rows: the weight of a row multiplies the A operand of the MFMA alone (one rounding of z * omega
+ * per entry of z, then M's exact products and sums); the plan, the work items, the scratch and the
+ * order of every sum are psgd_gramian's (psgd_gramian_plan describes this call too), so omega == 1.0
+ * everywhere returns psgd_gramian's bytes, and every property stated there holds: no floating-point
+ * atomics, the same bits from call to call, rows past a tile's end and pad columns never used,
+ * M_w == M_w^T bit for bit. CSR rows: a row's products are scaled by its weight before the fp64
+ * atomics; the three scalars sum w y^2, sum w y and sum w are per-tile sums merged in tile order and
+ * are reproducible.
+ * Errors, stream ordering, scratch and a registry of empty partitions are psgd_gramian's: PSGD_EINVAL
+ * for a null ctx or pointer, PSGD_ESTATE when no partition is registered, PSGD_EUNSUPPORTED for
+ * d > PSGD_GRAMIAN_MAX_D, zeros when the registered partitions hold no row. */
+int32_t psgd_gramian_weighted(psgd_ctx* ctx, const double* omega, double* out);
+int32_t psgd_gramian_weighted_device(psgd_ctx* ctx, const double* d_omega, double* d_out, void* stream);
+
+/* The curvature of the loss along every registered row's margin at weights w[d]: out[i] =
+ * d^2 loss / d(x_i . w)^2 for row i in local row order (psgd_local_rows doubles), one launch over all
+ * partitions, dense or CSR, f32 or f64 storage.
+ *   PSGD_GRADIENT_LOGISTIC: with z = x . w in fp64 (the stored values widened, fma along the features
+ *     as in psgd_evaluate), e = exp(-|z|) and h = e / ((1 + e)(1 + e)): exactly 0.25 at z = 0, exactly
+ *     0.0 once e underflows, never NaN for a finite z;
+ *   PSGD_GRADIENT_LEAST_SQUARES: 1.0;
+ *   PSGD_GRADIENT_HINGE: PSGD_EUNSUPPORTED (the curvature is 0 almost everywhere).
+ * The pad columns of a zero-copy row are never used. Every row is written once: the same bits from
+ * call to call. Errors: PSGD_EINVAL for a null ctx or pointer or an unknown gradient; PSGD_ESTATE when
+ * no partition is registered. Stream ordering and scratch are psgd_evaluate's. */
+int32_t psgd_row_curvature(psgd_ctx* ctx, int32_t gradient, const double* w, double* out);
+int32_t psgd_row_curvature_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double* d_out, void* stream);
+
 /* The row projection Y = X B over every registered row -- the pass behind MLlib 1.6.1's
  * RowMatrix.multiply and PCAModel.transform. B is d * k doubles, row-major (1 <= k <=
  * PSGD_PROJECT_MAX_K); Y[r][j] = sum_i x[r][i] B[i][j] with the stored values widened to double and

@@ -18,6 +18,7 @@ from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine,
                            evaluate, evaluate_multinomial, make_params, runParallelizedSGD)
 from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradient_sum_multinomial, runMiniBatchSGD,
                                runMiniBatchSGDMultinomial)
+from .newton import HessianSum, Newton, hessian_sum, runNewton
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
@@ -31,6 +32,7 @@ __all__ = [
     "BinaryClassificationMetrics", "MulticlassMetrics", "randomSplit", "kFold",
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "gradient_sum_multinomial", "runMiniBatchSGDMultinomial",
+    "Newton", "runNewton", "hessian_sum", "HessianSum",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
     "multiply", "computePrincipalComponents", "computeSVD", "PCA", "PCAModel",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",

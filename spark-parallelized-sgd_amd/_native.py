@@ -34,6 +34,8 @@ EXPORTED = (
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
     "psgd_gradient_sum_multinomial", "psgd_gradient_sum_multinomial_device", "psgd_gradient_multinomial_plan",
     "psgd_gramian", "psgd_gramian_device", "psgd_gramian_plan",
+    "psgd_gramian_weighted", "psgd_gramian_weighted_device", "psgd_local_rows",
+    "psgd_row_curvature", "psgd_row_curvature_device",
     "psgd_project", "psgd_project_device", "psgd_project_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
@@ -148,6 +150,11 @@ def lib():
             "psgd_gramian": ([vp, vp], C.c_int32),
             "psgd_gramian_device": ([vp, vp, vp], C.c_int32),
             "psgd_gramian_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
+            "psgd_gramian_weighted": ([vp, vp, vp], C.c_int32),
+            "psgd_gramian_weighted_device": ([vp, vp, vp, vp], C.c_int32),
+            "psgd_local_rows": ([vp, vp], C.c_int32),
+            "psgd_row_curvature": ([vp, C.c_int32, vp, vp], C.c_int32),
+            "psgd_row_curvature_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
             "psgd_project": ([vp, C.c_int64, C.c_int32, vp, vp], C.c_int32),
             "psgd_project_device": ([vp, C.c_int32, vp, C.c_int32, C.c_int64, vp, vp, vp], C.c_int32),
             "psgd_project_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
@@ -559,6 +566,43 @@ class Context:
     def gramian_device(self, out_ptr, stream=None):
         """psgd_gramian_device: enqueued on `stream`; out[(d + 2)^2] on the device."""
         check(self._L.psgd_gramian_device(self.handle, out_ptr, stream))
+
+    def local_rows(self) -> int:
+        """psgd_local_rows: the registered rows, the length of the per-row arrays below."""
+        n = C.c_int64()
+        check(self._L.psgd_local_rows(self.handle, C.byref(n)))
+        return int(n.value)
+
+    def gramian_weighted(self, d: int, omega):
+        """Host-pointer form (psgd_gramian_weighted): M_w = sum omega_i z_i z_i^T, omega one double per
+        registered row in local row order."""
+        import numpy as np
+        omega = np.ascontiguousarray(omega, dtype=np.float64)
+        if omega.ndim != 1 or omega.shape[0] != self.local_rows():
+            raise IllegalArgumentException(
+                f"requirement failed: the weighted Gramian takes one weight per registered row "
+                f"({self.local_rows()}; got shape {omega.shape})")
+        a = int(d) + 2
+        out = np.zeros((a, a), dtype=np.float64)
+        check(self._L.psgd_gramian_weighted(self.handle, omega.ctypes.data, out.ctypes.data))
+        return out
+
+    def gramian_weighted_device(self, omega_ptr, out_ptr, stream=None):
+        """psgd_gramian_weighted_device: enqueued on `stream`; omega[local rows], out[(d + 2)^2] on the device."""
+        check(self._L.psgd_gramian_weighted_device(self.handle, omega_ptr, out_ptr, stream))
+
+    # the rows' curvature ------------------------------------------------------------------------
+    def row_curvature(self, gradient: int, w):
+        """Host-pointer form (psgd_row_curvature): d^2 loss / d(x . w)^2 of every registered row."""
+        import numpy as np
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        out = np.zeros(max(self.local_rows(), 1), dtype=np.float64)
+        check(self._L.psgd_row_curvature(self.handle, int(gradient), w.ctypes.data, out.ctypes.data))
+        return out[: self.local_rows()]
+
+    def row_curvature_device(self, gradient: int, w_ptr, out_ptr, stream=None):
+        """psgd_row_curvature_device: enqueued on `stream`; out[local rows] on the device."""
+        check(self._L.psgd_row_curvature_device(self.handle, int(gradient), w_ptr, out_ptr, stream))
 
     # the row projection -------------------------------------------------------------------------
     def project(self, part: int, n_rows: int, B):

@@ -459,8 +459,9 @@ struct psgd_ctx {
     // host-pointer forms' staging
     DevBuf gdescs, grows, gys, gxstate, grec, gio;
     // the augmented Gramian (psgd_gramian): the dense items' records / the CSR tiles' scalar sums,
-    // and the host-pointer form's staging of M
-    DevBuf qrec, qio;
+    // and the host-pointer form's staging of M; the host-pointer forms' staging of the row weights
+    // (psgd_gramian_weighted) and of w with the rows' curvature (psgd_row_curvature)
+    DevBuf qrec, qio, qomega;
     // binary classification metrics (psgd_binary_counts*): the sort's pair buffers and tile tables
     // (with a table of the call's own and the model forms' margins), and the host-pointer forms' staging
     DevBuf mscratch, mio;
@@ -840,7 +841,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->eparts, &ctx->etiles, &ctx->epart, &ctx->ew, &ctx->emargins,
                           &ctx->stile0, &ctx->srec, &ctx->sio,
                           &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
-                          &ctx->qrec, &ctx->qio,
+                          &ctx->qrec, &ctx->qio, &ctx->qomega,
                           &ctx->mscratch, &ctx->mio, &ctx->cidx, &ctx->csel, &ctx->stab,
                           &ctx->watchdog})
             b->release();
@@ -2532,9 +2533,8 @@ static int32_t gramian_width(int32_t d) {
     return PSGD_OK;
 }
 
-int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream) {
-    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
-    if (!d_out) return fail(PSGD_EINVAL, "d_out is null");
+// d_omega: null for the plain Gramian, else one weight per registered row in local row order.
+static int32_t gramian_enqueue(psgd_ctx* ctx, const double* d_omega, double* d_out, void* stream) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
     const Part& first = ctx->parts.begin()->second;
@@ -2553,20 +2553,33 @@ int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream) {
     const psgd::GramGeom gm = psgd::gram_geometry(first.layout, storage, first.d, n_tiles, max_nnz);
     HIP_TRY(ctx->qrec.ensure((size_t)gm.scratch_bytes + sizeof(double)));
     const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>();
+    // the partitions' first rows in local row order, uploaded with the descriptors
+    const int64_t* row0 = d_omega ? ctx->cidx.as<int64_t>() + P : nullptr;
     const int e = first.layout == psgd::kCsr
                       ? psgd::launch_gramian_csr(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage,
-                                                 ctx->qrec.as<double>(), d_out, ctx->num_cus, st)
+                                                 ctx->qrec.as<double>(), d_out, ctx->num_cus, st, d_omega, row0)
                       : psgd::launch_gramian_dense(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage,
-                                                   ctx->qrec.as<double>(), d_out, st);
+                                                   ctx->qrec.as<double>(), d_out, st, d_omega, row0);
     if (e) return fail(PSGD_EDEVICE, std::string("Gramian launch failed: ") + hipGetErrorString((hipError_t)e));
     return PSGD_OK;
 }
 
-int32_t psgd_gramian(psgd_ctx* ctx, double* out) {
+int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream) {
     if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
-    if (!out) return fail(PSGD_EINVAL, "out is null");
-    size_t len = 0;
-    double* d_out = nullptr;
+    if (!d_out) return fail(PSGD_EINVAL, "d_out is null");
+    return gramian_enqueue(ctx, nullptr, d_out, stream);
+}
+
+int32_t psgd_gramian_weighted_device(psgd_ctx* ctx, const double* d_omega, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_omega || !d_out) return fail(PSGD_EINVAL, "d_omega/d_out are null");
+    return gramian_enqueue(ctx, d_omega, d_out, stream);
+}
+
+// The host-pointer forms: omega (null: the plain Gramian) staged in, M staged out.
+static int32_t gramian_host(psgd_ctx* ctx, const double* omega, double* out) {
+    size_t len = 0, n = 0;
+    double *d_out = nullptr, *d_omega = nullptr;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
@@ -2575,16 +2588,108 @@ int32_t psgd_gramian(psgd_ctx* ctx, double* out) {
         if (rc) return rc;
         len = ((size_t)d + 2) * ((size_t)d + 2);
         DeviceGuard g(ctx->device);
-        // (the staging buffer is scratch too: a call on another stream may still use it)
+        // (the staging buffers are scratch too: a call on another stream may still use them)
         rc = scratch_acquire(ctx, ctx->stream);
         if (rc) return rc;
         HIP_TRY(ctx->qio.ensure(len * sizeof(double)));
         d_out = ctx->qio.as<double>();
+        if (omega) {
+            for (auto& kv : ctx->parts) n += (size_t)kv.second.n_rows;
+            HIP_TRY(ctx->qomega.ensure(std::max<size_t>(n, 1) * sizeof(double)));
+            d_omega = ctx->qomega.as<double>();
+            if (n) HIP_TRY(hipMemcpyAsync(d_omega, omega, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            // the caller's array is pageable in general: the copy has left it when this returns
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
     }
-    int32_t rc = psgd_gramian_device(ctx, d_out, ctx->stream);
+    int32_t rc = gramian_enqueue(ctx, d_omega, d_out, ctx->stream);
     if (rc) return rc;
     DeviceGuard g(ctx->device);
     HIP_TRY(hipMemcpyAsync(out, d_out, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_gramian(psgd_ctx* ctx, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    return gramian_host(ctx, nullptr, out);
+}
+
+int32_t psgd_gramian_weighted(psgd_ctx* ctx, const double* omega, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!omega || !out) return fail(PSGD_EINVAL, "omega/out are null");
+    return gramian_host(ctx, omega, out);
+}
+
+int32_t psgd_local_rows(psgd_ctx* ctx, int64_t* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int64_t n = 0;
+    for (auto& kv : ctx->parts) n += kv.second.n_rows;
+    *out = n;
+    return PSGD_OK;
+}
+
+// ---- The rows' curvature (kernels in psgd_hessian.hip) ----
+static int32_t curvature_kind(int32_t gradient) {
+    if (gradient < PSGD_GRADIENT_LOGISTIC || gradient > PSGD_GRADIENT_HINGE)
+        return fail(PSGD_EINVAL, "unknown gradient kind " + std::to_string(gradient));
+    if (gradient == PSGD_GRADIENT_HINGE)
+        return fail(PSGD_EUNSUPPORTED, "the hinge loss has no curvature: it is 0 almost everywhere");
+    return PSGD_OK;
+}
+
+int32_t psgd_row_curvature_device(psgd_ctx* ctx, int32_t gradient, const double* d_w, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = curvature_kind(gradient);
+    if (rc) return rc;
+    if (!d_w || !d_out) return fail(PSGD_EINVAL, "d_w/d_out are null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const Part& first = ctx->parts.begin()->second;
+    const int P = (int)ctx->parts.size();
+    const std::vector<psgd::EvalPart>& ep = ctx->eval_parts;
+    const int e = psgd::launch_row_curvature(ctx->descs.as<psgd::ChainDesc>(), ctx->eparts.as<psgd::EvalPart>(),
+                                             ctx->cidx.as<int64_t>() + P, P, ep[P].tile0 - ep[0].tile0,
+                                             ctx->row_off.back(), first.layout, first.dtype == PSGD_F32 ? 1 : 0,
+                                             gradient, d_w, first.d, d_out, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("curvature launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_row_curvature(psgd_ctx* ctx, int32_t gradient, const double* w, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    int32_t rc = curvature_kind(gradient);
+    if (rc) return rc;
+    if (!w || !out) return fail(PSGD_EINVAL, "w/out are null");
+    size_t d = 0, n = 0;
+    double *d_w = nullptr, *d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        d = (size_t)ctx->parts.begin()->second.d;
+        for (auto& kv : ctx->parts) n += (size_t)kv.second.n_rows;
+        DeviceGuard g(ctx->device);
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->qomega.ensure((d + std::max<size_t>(n, 1)) * sizeof(double)));
+        d_w = ctx->qomega.as<double>();
+        d_out = d_w + d;
+        HIP_TRY(hipMemcpyAsync(d_w, w, d * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    rc = psgd_row_curvature_device(ctx, gradient, d_w, d_out, ctx->stream);
+    if (rc) return rc;
+    if (n == 0) return PSGD_OK;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return PSGD_OK;
 }

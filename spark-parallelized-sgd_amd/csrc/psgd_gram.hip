@@ -2,7 +2,10 @@
 // z_i = [x_i0 .. x_i,d-1, y_i, 1] (a = d + 2 columns) it returns M = sum_i z_i z_i^T, a x a doubles,
 // row-major, both triangles (the lower an exact copy of the upper). X^T X = M[:d, :d], X^T y =
 // M[:d, d], y^T y = M[d, d], the column sums M[:d, d + 1], sum y = M[d, d + 1], the row count
-// M[d + 1, d + 1]. All arithmetic is fp64 whatever the storage.
+// M[d + 1, d + 1]. All arithmetic is fp64 whatever the storage. With a weight per row
+// (psgd_gramian_weighted) the same kernels return M_w = sum_i w_i z_i z_i^T in the same layout: the
+// Hessian of a loss sum when w is the rows' curvature (psgd_hessian.hip), weighted least squares' moments
+// when w are instance weights.
 //
 // The tiling is the statistics passes' (tile0[p] is partition p's first tile, numbered across the
 // partitions in partition-index order), as in psgd_grad.hip.
@@ -46,10 +49,24 @@ typedef double gram_d4 __attribute__((ext_vector_type(4)));
 // First kept group of group row R: the first whose last block column reaches the row's first block.
 __host__ __device__ inline int gram_first_group(int R, int gr, int gc) { return R * gr / gc; }
 
-template <typename S, int GR, int GC>
+// W: the row-weighted pass M_w = sum_i w_i z_i z_i^T. omega holds one double per registered row in
+// local row order, row0[p] is partition p's first row in it. The weight of a fragment's row comes
+// with its label and multiplies the A operand alone (a[r] = valid ? v * w : 0.0; b[c] is z as it
+// is): one v_mul_f64 per row fragment and sub-step, one rounding of z * w before the MFMA's exact
+// products are added. Groups, spans, records and the order of every sum are the unweighted pass's, so
+// omega == 1.0 everywhere gives its bits.
+// The weights are a trailing parameter pack (none, or one GramOmega) so that the unweighted kernel's
+// arguments, and with them its code, are what they were.
+struct GramOmega {
+    const double* omega;
+    const int64_t* row0;
+};
+template <typename S, int GR, int GC, typename... Om>
 __global__ __launch_bounds__(kGramBlock, 1) void gram_dense(const ChainDesc* __restrict__ descs,
                                                            const int64_t* __restrict__ tile0, int P,
-                                                           int64_t n_tiles, GramGeom gm, double* __restrict__ rec) {
+                                                           int64_t n_tiles, GramGeom gm, double* __restrict__ rec,
+                                                           Om... om) {
+    constexpr bool W = sizeof...(Om) == 1;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t item = (int64_t)blockIdx.x * kGramWaves + wave;
@@ -112,12 +129,18 @@ __global__ __launch_bounds__(kGramBlock, 1) void gram_dense(const ChainDesc* __r
         const int64_t r1 = r0 + gm.tile_rows < dsc.n_rows ? r0 + gm.tile_rows : dsc.n_rows;
         if (r1 <= r0) continue;
         const S* X = reinterpret_cast<const S*>(dsc.x);
+        const double* orow = nullptr;
+        if constexpr (W) {
+            const GramOmega go = (om, ...);
+            orow = go.omega + go.row0[p];
+        }
         // A stage's loads carry no branch and no conversion, so that they stay in flight under the
         // MFMAs of the stage before: a row past the tile's end loads the tile's last row, a column
         // >= d feature d - 1 (plain loads: the other groups' waves of this span read the same
         // lines from L2), and the label comes with every sub-step. z[row][col] is selected from
         // them at its use: nothing loaded at a column >= d or a row >= r1 reaches an MFMA.
-        auto load = [&](S (&fa)[kGramSub][GR], S (&fb)[kGramSub][GC], double (&fy)[kGramSub], int64_t rb) __attribute__((always_inline)) {
+        auto load = [&](S (&fa)[kGramSub][GR], S (&fb)[kGramSub][GC], double (&fy)[kGramSub],
+                        double (&fo)[kGramSub], int64_t rb) __attribute__((always_inline)) {
 #pragma unroll
             for (int s = 0; s < kGramSub; ++s) {
                 const int64_t row = rb + 4 * s + kq;
@@ -128,6 +151,7 @@ __global__ __launch_bounds__(kGramBlock, 1) void gram_dense(const ChainDesc* __r
 #pragma unroll
                 for (int c = 0; c < GC; ++c) fb[s][c] = xr[lb[c]];
                 fy[s] = as_global(dsc.y)[rr];
+                if constexpr (W) fo[s] = as_global(orow)[rr];
             }
         };
         // (a fragment of features alone takes one select; the lane tests of the others are made where
@@ -141,7 +165,14 @@ __global__ __launch_bounds__(kGramBlock, 1) void gram_dense(const ChainDesc* __r
             }
             return valid ? v : 0.0;
         };
-        auto compute = [&](const S (&fa)[kGramSub][GR], const S (&fb)[kGramSub][GC], const double (&fy)[kGramSub], int64_t rb) __attribute__((always_inline)) {
+        // (the weighted A operand: the selected z times the row's weight, then the row mask -- a row
+        // past the tile's end gives 0.0 by selection, whatever weight was loaded for it)
+        auto select_w = [&](S x, double y, double o, int col, bool valid, bool all_features) __attribute__((always_inline)) -> double {
+            const double v = select(x, y, col, true, all_features) * o;
+            return valid ? v : 0.0;
+        };
+        auto compute = [&](const S (&fa)[kGramSub][GR], const S (&fb)[kGramSub][GC], const double (&fy)[kGramSub],
+                           const double (&fo)[kGramSub], int64_t rb) __attribute__((always_inline)) {
             // (the masks are re-read here as scalars: hoisted out of the loop their tests are kept as
             // lane masks, one each, and spill the scalar registers)
             unsigned onl = __builtin_amdgcn_readfirstlane(on);
@@ -153,7 +184,10 @@ __global__ __launch_bounds__(kGramBlock, 1) void gram_dense(const ChainDesc* __r
                 const bool valid = rb + 4 * s + kq < r1;
                 double a[GR], b[GC];
 #pragma unroll
-                for (int r = 0; r < GR; ++r) a[r] = select(fa[s][r], fy[s], ca[r], valid, (pl >> r) & 1u);
+                for (int r = 0; r < GR; ++r) {
+                    if constexpr (W) a[r] = select_w(fa[s][r], fy[s], fo[s], ca[r], valid, (pl >> r) & 1u);
+                    else a[r] = select(fa[s][r], fy[s], ca[r], valid, (pl >> r) & 1u);
+                }
 #pragma unroll
                 for (int c = 0; c < GC; ++c) b[c] = select(fb[s][c], fy[s], cb[c], valid, (pl >> (GR + c)) & 1u);
 #pragma unroll
@@ -169,15 +203,16 @@ __global__ __launch_bounds__(kGramBlock, 1) void gram_dense(const ChainDesc* __r
         constexpr int64_t stage = 4 * kGramSub;
         S xa[kGramSub][GR], xb[kGramSub][GC], ya[kGramSub][GR], yb[kGramSub][GC];
         double xy[kGramSub], yy[kGramSub];
+        double xo[kGramSub], yo[kGramSub];   // (W only: dead, and gone, in the unweighted kernel)
         int64_t rb = r0;
-        load(xa, xb, xy, rb);
+        load(xa, xb, xy, xo, rb);
         while (rb < r1) {
-            load(ya, yb, yy, rb + stage);
-            compute(xa, xb, xy, rb);
+            load(ya, yb, yy, yo, rb + stage);
+            compute(xa, xb, xy, xo, rb);
             rb += stage;
             if (rb >= r1) break;
-            load(xa, xb, xy, rb + stage);
-            compute(ya, yb, yy, rb);
+            load(xa, xb, xy, xo, rb + stage);
+            compute(ya, yb, yy, yo, rb);
             rb += stage;
         }
     }
@@ -213,10 +248,13 @@ __global__ __launch_bounds__(kGramBlock) void gram_merge(const double* __restric
 }
 
 // ---- CSR ----
-template <typename S>
+// W: every outer product is scaled by its row's weight (vp takes it) and the three scalars become
+// sum w y^2, sum w y and sum w.
+template <typename S, typename... Om>
 __global__ __launch_bounds__(kGramBlock) void gram_csr(const ChainDesc* __restrict__ descs,
                                                        const int64_t* __restrict__ tile0, int P, int64_t n_tiles,
-                                                       GramGeom gm, double* out, double* __restrict__ rec) {
+                                                       GramGeom gm, double* out, double* __restrict__ rec, Om... om) {
+    constexpr bool W = sizeof...(Om) == 1;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int gl = gm.group, rpw = 64 / gl;
@@ -237,9 +275,15 @@ __global__ __launch_bounds__(kGramBlock) void gram_csr(const ChainDesc* __restri
                 const int64_t b = dsc.row_ptr[r];
                 const int n = (int)(dsc.row_ptr[r + 1] - b);
                 const double y = dsc.y[r];
+                double o = 1.0;
+                if constexpr (W) {
+                    const GramOmega go = (om, ...);
+                    o = go.omega[go.row0[p] + r];
+                }
                 // entry p against entries p .., the label (q = n) and the ones column (q = n + 1)
                 for (int pi = 0; pi < n; ++pi) {
-                    const double vp = (double)val[b + pi];
+                    double vp = (double)val[b + pi];
+                    if constexpr (W) vp = vp * o;
                     double* row = out + (int64_t)dsc.col[b + pi] * a;
                     for (int q = pi + j; q < n + 2; q += gl) {
                         const int cq = q < n ? dsc.col[b + q] : d + (q - n);
@@ -248,9 +292,16 @@ __global__ __launch_bounds__(kGramBlock) void gram_csr(const ChainDesc* __restri
                     }
                 }
                 if (j == 0) {
-                    yy += y * y;
-                    sy += y;
-                    cnt += 1.0;
+                    if constexpr (W) {
+                        const double oy = o * y;
+                        yy += oy * y;
+                        sy += oy;
+                        cnt += o;
+                    } else {
+                        yy += y * y;
+                        sy += y;
+                        cnt += 1.0;
+                    }
                 }
             }
         }
@@ -315,9 +366,23 @@ int launch_mfma_rate(int blocks, int iters, double* out, hipStream_t st) {
 
 template <typename S>
 int launch_dense_s(const GramGeom& gm, hipStream_t st, const ChainDesc* descs, const int64_t* tile0, int P,
-                   int64_t n_tiles, double* rec) {
+                   int64_t n_tiles, double* rec, const double* omega, const int64_t* row0) {
     const int64_t items = gm.n_spans * gm.n_groups;
     const dim3 gr((unsigned)((items + kGramWaves - 1) / kGramWaves)), bl(kGramBlock);
+    if (omega) {
+        const GramOmega go{omega, row0};
+        if (gm.gr == 1 && gm.gc == 1)
+            hipLaunchKernelGGL((gram_dense<S, 1, 1, GramOmega>), gr, bl, 0, st, descs, tile0, P, n_tiles, gm, rec, go);
+        else if (gm.gr == 1 && gm.gc == 2)
+            hipLaunchKernelGGL((gram_dense<S, 1, 2, GramOmega>), gr, bl, 0, st, descs, tile0, P, n_tiles, gm, rec, go);
+        else if (gm.gr == 2 && gm.gc == 4)
+            hipLaunchKernelGGL((gram_dense<S, 2, 4, GramOmega>), gr, bl, 0, st, descs, tile0, P, n_tiles, gm, rec, go);
+        else if (gm.gr == 4 && gm.gc == 8)
+            hipLaunchKernelGGL((gram_dense<S, 4, 8, GramOmega>), gr, bl, 0, st, descs, tile0, P, n_tiles, gm, rec, go);
+        else
+            return (int)hipErrorInvalidValue;
+        return (int)hipGetLastError();
+    }
     if (gm.gr == 1 && gm.gc == 1)
         hipLaunchKernelGGL((gram_dense<S, 1, 1>), gr, bl, 0, st, descs, tile0, P, n_tiles, gm, rec);
     else if (gm.gr == 1 && gm.gc == 2)
@@ -379,10 +444,11 @@ GramGeom gram_geometry(int layout, int storage, int d, int64_t n_tiles, int64_t 
 }
 
 int launch_gramian_dense(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
-                         const GramGeom& gm, int storage, double* rec, double* out, hipStream_t st) {
+                         const GramGeom& gm, int storage, double* rec, double* out, hipStream_t st,
+                         const double* omega, const int64_t* row0) {
     if (n_tiles <= 0) return (int)hipMemsetAsync(out, 0, (size_t)gm.a * gm.a * sizeof(double), st);
-    const int e = storage == 1 ? launch_dense_s<float>(gm, st, descs, tile0, n_parts, n_tiles, rec)
-                               : launch_dense_s<double>(gm, st, descs, tile0, n_parts, n_tiles, rec);
+    const int e = storage == 1 ? launch_dense_s<float>(gm, st, descs, tile0, n_parts, n_tiles, rec, omega, row0)
+                               : launch_dense_s<double>(gm, st, descs, tile0, n_parts, n_tiles, rec, omega, row0);
     if (e) return e;
     hipLaunchKernelGGL(gram_merge, dim3((unsigned)((gm.a + kGramBlock - 1) / kGramBlock), (unsigned)gm.a),
                        dim3(kGramBlock), 0, st, rec, gm, out);
@@ -390,11 +456,18 @@ int launch_gramian_dense(const ChainDesc* descs, const int64_t* tile0, int n_par
 }
 
 int launch_gramian_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
-                       const GramGeom& gm, int storage, double* rec, double* out, int num_cus, hipStream_t st) {
+                       const GramGeom& gm, int storage, double* rec, double* out, int num_cus, hipStream_t st,
+                       const double* omega, const int64_t* row0) {
     int e = (int)hipMemsetAsync(out, 0, (size_t)gm.a * gm.a * sizeof(double), st);
     if (e || n_tiles <= 0) return e;
     const unsigned blocks = grad_balanced_blocks(n_tiles, num_cus, 8);
-    if (storage == 1)
+    if (omega && storage == 1)
+        hipLaunchKernelGGL((gram_csr<float, GramOmega>), dim3(blocks), dim3(kGramBlock), 0, st, descs, tile0, n_parts,
+                           n_tiles, gm, out, rec, GramOmega{omega, row0});
+    else if (omega)
+        hipLaunchKernelGGL((gram_csr<double, GramOmega>), dim3(blocks), dim3(kGramBlock), 0, st, descs, tile0, n_parts,
+                           n_tiles, gm, out, rec, GramOmega{omega, row0});
+    else if (storage == 1)
         hipLaunchKernelGGL(gram_csr<float>, dim3(blocks), dim3(kGramBlock), 0, st, descs, tile0, n_parts, n_tiles, gm,
                            out, rec);
     else

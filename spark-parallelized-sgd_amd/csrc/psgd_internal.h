@@ -360,10 +360,21 @@ GramGeom gram_geometry(int layout, int storage, int d, int64_t n_tiles, int64_t 
 int gram_groups(int nb, int gr, int gc);
 // out[a * a] = M over the rows of descs[0 .. n_parts); rec is gm.scratch_bytes of scratch. Dense: no
 // floating-point atomics, reproducible bits. CSR: out is the accumulator of fp64 atomics.
+// omega != nullptr: the row-weighted M_w = sum_i omega_i z_i z_i^T, omega one double per registered row
+// in local row order and row0[p] partition p's first row in it (the same plan, records and order).
 int launch_gramian_dense(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
-                         const GramGeom& gm, int storage, double* rec, double* out, hipStream_t st);
+                         const GramGeom& gm, int storage, double* rec, double* out, hipStream_t st,
+                         const double* omega = nullptr, const int64_t* row0 = nullptr);
 int launch_gramian_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
-                       const GramGeom& gm, int storage, double* rec, double* out, int num_cus, hipStream_t st);
+                       const GramGeom& gm, int storage, double* rec, double* out, int num_cus, hipStream_t st,
+                       const double* omega = nullptr, const int64_t* row0 = nullptr);
+
+// ---- The rows' curvature (psgd_hessian.hip: psgd_row_curvature) ----
+// out[row0[p] + r] = d^2 loss / d(x . w)^2 of row r of partition p at weights w[d], over the scoring
+// passes' tiling (EvalPart), n_rows rows in all. gradient: G_LOGISTIC or G_LEAST_SQUARES.
+int launch_row_curvature(const ChainDesc* descs, const EvalPart* ep, const int64_t* row0, int n_parts,
+                         int64_t n_items, int64_t n_rows, int layout, int storage, int gradient, const double* w,
+                         int d, double* out, int num_cus, hipStream_t st);
 
 // ---- The row projection Y = X B (psgd_project.hip: psgd_project) ----
 // The plan of a call: host code, no device (psgd_project_plan reports it).

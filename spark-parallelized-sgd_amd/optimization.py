@@ -721,24 +721,79 @@ class HipEngine(ShardedEngine):
                                lambda w_ptr, out: self.ctx.gradient_sum_multinomial_device(
                                    K, w_ptr, miniBatchFraction, iteration, out, self.stream.cuda_stream))
 
-    # the augmented Gramian (psgd_gramian_device) ------------------------------------------------
-    def gramian(self):
+    # the augmented Gramian (psgd_gramian_device / psgd_gramian_weighted_device) ------------------
+    def local_rows(self) -> int:
+        """The rows of this rank's partitions: the length of row_curvature()'s result and of
+        gramian()'s weights."""
+        return sum(self._data.partitions[p].n_rows for p in range(self.lo, self.hi))
+
+    def gramian(self, weights=None):
         """M = sum_i z_i z_i^T with z_i = [x_i, y_i, 1] over every row of the data, on all ranks, as a
         device tensor of (d + 2)^2 doubles, row-major (include/psgd.h has the semantics; stat.Gramian
         reads it). Each rank runs its partitions; the ranks all-gather their matrices (the backends of
         exchange()) and every rank adds them in rank order (merge_gradient_sums: a loop, not a tree),
-        so all ranks hold the same bits; a rank without partitions contributes zeros."""
+        so all ranks hold the same bits; a rank without partitions contributes zeros.
+        weights: a device tensor of local_rows() doubles, one per row of this rank's partitions in
+        partition and iterator order -- the result is then M_w = sum_i weights_i z_i z_i^T
+        (psgd_gramian_weighted_device), the ranks' matrices added in the same way."""
         nf = self._data.num_features
         if nf > N.GRAMIAN_MAX_D:
             raise N.IllegalArgumentException(
                 f"requirement failed: the Gramian takes at most {N.GRAMIAN_MAX_D} features (got {nf})")
-        return self._batch_sum((nf + 2) * (nf + 2), None, None,
-                               lambda _w, out: self.ctx.gramian_device(out, self.stream.cuda_stream))
+        if weights is None:
+            return self._batch_sum((nf + 2) * (nf + 2), None, None,
+                                   lambda _w, out: self.ctx.gramian_device(out, self.stream.cuda_stream))
+        return self._batch_sum((nf + 2) * (nf + 2), self._row_weights, weights,
+                               lambda om, out: self.ctx.gramian_weighted_device(om, out, self.stream.cuda_stream))
 
-    def _batch_sum(self, width: int, to_device, w, call):
+    def device_rows(self, values):
+        """A host array of local_rows() doubles as a device tensor (gramian()'s weights)."""
+        with self.torch.cuda.stream(self.stream):
+            t = self.torch.from_numpy(np.array(values, dtype=np.float64)).to(self.dev)   # (a copy: torch wants it writable)
+        self.stream.synchronize()
+        return t
+
+    def _row_weights(self, weights):
+        """weights as a contiguous f64 device tensor of local_rows() entries (self.stream is current)."""
+        if not self.torch.is_tensor(weights):
+            raise IllegalArgumentException(
+                "requirement failed: HipEngine.gramian takes its row weights as a device tensor "
+                "(stat.gramian takes a host array)")
+        om = weights.detach().to(device=self.dev, dtype=self.torch.float64).contiguous()
+        n = self.local_rows()
+        if om.dim() != 1 or om.shape[0] != n:
+            raise IllegalArgumentException(
+                f"requirement failed: the weighted Gramian takes one weight per local row ({n}; got shape "
+                f"{tuple(om.shape)})")
+        if n == 0:   # (a valid pointer for a registry of empty partitions)
+            om = self.torch.zeros(1, dtype=self.torch.float64, device=self.dev)
+        return om
+
+    # the rows' curvature (psgd_row_curvature_device) ----------------------------------------------
+    def row_curvature(self, gradient, w):
+        """h_i = d^2 loss / d(x_i . w)^2 of every row of this rank's partitions at weights w (a host
+        array or a device tensor of num_features doubles), as a device tensor of local_rows() doubles
+        in partition and iterator order: what gramian(weights=) takes to give the Hessian of the loss
+        sum (include/psgd.h has the values). The rows are this rank's own, so the ranks exchange
+        nothing here. HingeGradient raises UnsupportedOperationException, and so does the multinomial
+        LogisticGradient (numClasses > 2)."""
+        if num_classes(gradient) > 2:
+            raise N.UnsupportedOperationException(
+                "row_curvature takes a binary gradient: the multinomial LogisticGradient (numClasses > 2) "
+                "has a matrix of curvatures per row")
+        kind = gradient_kind(gradient)
+        if kind == 2:   # PSGD_GRADIENT_HINGE
+            raise N.UnsupportedOperationException(
+                "HingeGradient has no curvature: its second derivative is 0 almost everywhere")
+        return self._batch_sum(max(self.local_rows(), 1), self._score_weights, w,
+                               lambda w_ptr, out: self.ctx.row_curvature_device(
+                                   kind, w_ptr, out, self.stream.cuda_stream), local=True)[: self.local_rows()]
+
+    def _batch_sum(self, width: int, to_device, w, call, local: bool = False):
         """call(w_ptr, out_ptr) over this rank's partitions into `width` zeroed doubles, then the ranks'
-        all-gather and the rank-order sum. to_device(w) puts the weights on the device; None for a pass
-        that takes no weights (w_ptr is then None)."""
+        all-gather and the rank-order sum (not for a `local` result, which is this rank's alone).
+        to_device(w) puts the weights on the device; None for a pass that takes no weights (w_ptr is
+        then None)."""
         torch = self.torch
         caller = torch.cuda.current_stream(self.dev)
         self.stream.wait_stream(caller)
@@ -750,7 +805,7 @@ class HipEngine(ShardedEngine):
                     if self.ctx.registered_token != self._key:
                         self._register(self._data)
                     call(None if w_dev is None else w_dev.data_ptr(), buf.data_ptr())
-            if self.world > 1:
+            if self.world > 1 and not local:
                 import torch.distributed as dist
                 out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
                 if dist.get_backend() == "gloo":

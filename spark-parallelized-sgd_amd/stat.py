@@ -6,6 +6,8 @@ follows from it on the host -- RowMatrix.computeGramianMatrix / computeCovarianc
   g.gram, g.xty, g.yty               # X^T X, X^T y, y^T y
   g.covariance(), g.corr()           # computeCovariance, Statistics.corr(., "pearson")
   w_star = g.normal_equations(regParam=0.1)
+  gw = gramian(data, weights=omega)  # sum omega_i z z^T: weighted least squares (WeightedLeastSquares, "normal")
+  gw.weightSum, gw.normal_equations(regParam=0.1)
   pc, explained = g.principal_components(k)   # RowMatrix.computePrincipalComponents
   s, V = g.svd(k)                             # RowMatrix.computeSVD, local-eigs mode
   projected = multiply(data, pc)              # RowMatrix.multiply: new rows on the device
@@ -59,9 +61,12 @@ def _eigh_desc(A: np.ndarray):
 
 class Gramian:
     """A host object over M = sum_i z_i z_i^T, z_i = [x_i0 .. x_i,d-1, y_i, 1]: a symmetric
-    (d + 2) x (d + 2) array of doubles."""
+    (d + 2) x (d + 2) array of doubles. weighted: the matrix is M_w = sum_i omega_i z_i z_i^T of row
+    weights omega (gramian(data, weights=)): M[d + 1, d + 1] is then their sum, weightSum, mean and
+    normal_equations divide by it (weighted least squares), and the members that need the row count
+    (covariance, corr, principal_components, svd) raise IllegalArgumentException."""
 
-    def __init__(self, matrix):
+    def __init__(self, matrix, weighted: bool = False):
         m = np.array(matrix, dtype=np.float64)
         if m.ndim == 1:
             a = int(round(np.sqrt(m.size)))
@@ -73,10 +78,21 @@ class Gramian:
                 f"requirement failed: the augmented Gramian is (d + 2) x (d + 2) with d >= 1 (got shape {m.shape})")
         self.matrix = m
         self.d = m.shape[0] - 2
+        self.weighted = bool(weighted)
 
     @property
     def count(self) -> int:
         return int(self.matrix[self.d + 1, self.d + 1])
+
+    @property
+    def weightSum(self) -> float:
+        """M[d + 1, d + 1]: the sum of the row weights (the row count of an unweighted Gramian)."""
+        return float(self.matrix[self.d + 1, self.d + 1])
+
+    def _unweighted(self, what: str) -> None:
+        if self.weighted:
+            raise IllegalArgumentException(
+                f"requirement failed: {what} needs the row count, which a weighted Gramian does not hold")
 
     @property
     def gram(self) -> np.ndarray:
@@ -101,6 +117,10 @@ class Gramian:
 
     @property
     def mean(self) -> np.ndarray:
+        if self.weighted:
+            if not self.weightSum > 0.0:
+                raise IllegalArgumentException("requirement failed: the weighted mean needs a positive weight sum")
+            return self.columnSums / self.weightSum
         n = self.count
         if n <= 0:
             raise IllegalArgumentException("requirement failed: Cannot compute the mean of a RowMatrix without rows.")
@@ -108,6 +128,7 @@ class Gramian:
 
     def covariance(self) -> np.ndarray:
         """RowMatrix.computeCovariance: cov_jk = G_jk / (n - 1) - (n / (n - 1)) mean_j mean_k."""
+        self._unweighted("covariance")
         n = self.count
         if n <= 1:
             raise IllegalArgumentException(
@@ -118,6 +139,7 @@ class Gramian:
     def corr(self) -> np.ndarray:
         """Statistics.corr(., "pearson"): sigma_j = sqrt(cov_jj), taken as 0 where |cov_jj| <= 1e-12;
         corr_jk = cov_jk / (sigma_j sigma_k), NaN where either sigma is 0; the diagonal is 1.0 always."""
+        self._unweighted("corr")
         cov = self.covariance()
         var = np.diag(cov)
         with np.errstate(invalid="ignore"):
@@ -132,13 +154,21 @@ class Gramian:
     def normal_equations(self, regParam: float = 0.0) -> np.ndarray:
         """The minimiser of what LeastSquaresGradient with SquaredL2SGDUpdater minimises,
         (1 / n) sum (w . x - y)^2 / 2 + (regParam / 2) ||w||^2: (G / n + regParam I) w = X^T y / n,
-        solved by Cholesky in fp64. A matrix that is not positive definite raises."""
+        solved by Cholesky in fp64. A matrix that is not positive definite raises. On a weighted
+        Gramian n is weightSum: the minimiser of (1 / W) sum omega_i (w . x_i - y_i)^2 / 2 + (regParam / 2)
+        ||w||^2, weighted least squares."""
         lam = float(regParam)
         if not lam >= 0.0:
             raise IllegalArgumentException(f"requirement failed: regParam must be nonnegative but got {regParam}")
-        n = self.count
-        if n <= 0:
-            raise IllegalArgumentException("requirement failed: the normal equations need at least one row")
+        if self.weighted:
+            n = self.weightSum
+            if not n > 0.0:
+                raise IllegalArgumentException(
+                    "requirement failed: the weighted normal equations need a positive weight sum")
+        else:
+            n = self.count
+            if n <= 0:
+                raise IllegalArgumentException("requirement failed: the normal equations need at least one row")
         A = self.gram / float(n) + lam * np.eye(self.d)
         b = self.xty / float(n)
         try:
@@ -155,6 +185,7 @@ class Gramian:
         in descending eigenvalue order, each with its largest-magnitude entry positive (this project's
         convention; MLlib leaves the sign to LAPACK); explainedVariance[j] is eigenvalue j over the
         trace (MLlib 2.0's member). Needs 1 <= k <= d and at least 2 rows."""
+        self._unweighted("principal_components")
         k = _check_k(k, self.d, "computePrincipalComponents")
         w, V = _eigh_desc(self.covariance())
         total = float(np.sum(w))
@@ -169,6 +200,7 @@ class Gramian:
         An eigenvalue at or below the fp64 eigen-solver's noise floor, d * 2^-52 * sigma_0^2 (the
         tolerance of numpy.linalg.matrix_rank), counts as zero whatever rCond is: the square root of
         such noise is about 1e-8 sigma_0 and would pass rCond = 1e-9 as a singular value."""
+        self._unweighted("svd")
         k = _check_k(k, self.d, "computeSVD")
         if not 0.0 <= float(rCond) <= 1.0:
             raise IllegalArgumentException(f"requirement failed: rCond must be within [0, 1] but got {rCond}")
@@ -183,14 +215,36 @@ class Gramian:
         return sigma[:keep].copy(), np.ascontiguousarray(V[:, :keep])
 
     def __repr__(self) -> str:
+        if self.weighted:
+            return f"Gramian(d={self.d}, weightSum={self.weightSum})"
         return f"Gramian(d={self.d}, count={self.count})"
 
 
-def gramian(data: PartitionedData, *, engine=None) -> Gramian:
+def _check_row_weights(data: PartitionedData, weights) -> np.ndarray:
+    """One finite, non-negative double per row of `data`, in partition order."""
+    om = np.ascontiguousarray(weights, dtype=np.float64)
+    if om.ndim != 1 or om.shape[0] != data.count():
+        raise IllegalArgumentException(
+            f"requirement failed: weights must hold one value per row ({data.count()}; got shape {om.shape})")
+    if not (np.all(np.isfinite(om)) and np.all(om >= 0.0)):
+        raise IllegalArgumentException("requirement failed: weights must be finite and nonnegative")
+    return om
+
+
+def local_row_slice(data: PartitionedData, engine) -> slice:
+    """The rows of the engine's partitions [lo, hi) within the data's rows in partition order."""
+    sizes = [p.n_rows for p in data.partitions]
+    return slice(sum(sizes[: engine.lo]), sum(sizes[: engine.hi]))
+
+
+def gramian(data: PartitionedData, weights=None, *, engine=None) -> Gramian:
     """The augmented Gramian of every row of every partition, on all ranks (HipEngine.gramian). Data
-    without rows raises IllegalArgumentException, as column_stats does."""
+    without rows raises IllegalArgumentException, as column_stats does. weights: a host array of
+    data.count() non-negative doubles in partition order (each rank takes the slice of its
+    partitions): the result is the weighted Gramian sum_i weights_i z_i z_i^T."""
     if data.num_partitions == 0 or data.count() == 0:
         raise IllegalArgumentException("requirement failed: Cannot compute the Gramian of data without rows.")
+    om = None if weights is None else _check_row_weights(data, weights)
     if engine is None:
         from . import _native as N
         if data.num_features > N.GRAMIAN_MAX_D:
@@ -200,7 +254,10 @@ def gramian(data: PartitionedData, *, engine=None) -> Gramian:
         rank, world, _ = _dist()
         engine = HipEngine(data, rank, world)
     a = data.num_features + 2
-    return Gramian(engine.gramian().cpu().numpy().reshape(a, a))
+    if om is None:
+        return Gramian(engine.gramian().cpu().numpy().reshape(a, a))
+    local = engine.device_rows(om[local_row_slice(data, engine)])
+    return Gramian(engine.gramian(weights=local).cpu().numpy().reshape(a, a), weighted=True)
 
 
 def covariance(data: PartitionedData, *, engine=None) -> np.ndarray:
