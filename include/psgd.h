@@ -524,6 +524,64 @@ int32_t psgd_project(psgd_ctx* ctx, int64_t part, int32_t k, const double* B, do
 #define PSGD_PROJECT_PLAN_LEN 8
 int32_t psgd_project_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t max_nnz, int64_t* out);
 
+/* Lloyd's iteration of k-means over every registered row -- the passes behind MLlib 1.6.1's KMeans
+ * (runs = 1) and KMeansModel.predict / computeCost. The centres are k * d doubles, row-major (1 <= k <=
+ * PSGD_KMEANS_MAX_K). All arithmetic is fp64 whatever the storage. For a row x: g_j = x . c_j (one fma
+ * chain along the features), cn_j = ||c_j||^2 (one fma chain, once a call), s_j = fma(-2, g_j, cn_j);
+ * the assignment a is the smallest j that minimises s_j (strict <: ties go to the lowest index, as
+ * findClosest does); xn = ||x||^2; dist2 = max(xn + s_a, 0), fastSquaredDistance's expanded form. NaN
+ * and Inf are outside the contract. The labels are not read; a CSR row's absent entries are zeros; the
+ * pad columns of a zero-copy row (ld > d) never reach the arithmetic.
+ * psgd_kmeans_assign writes assign[r] (int32) and dist2[r] (nullable) for the psgd_local_rows rows in
+ * local row order (partition-index order, then iterator order: psgd_row_curvature's).
+ * psgd_kmeans_step returns k (d + 1) + 2 doubles: sums[j][0 .. d) = the sum of the rows assigned to j,
+ * counts[j] (exact), cost = the sum of dist2, n = the row count. It runs the assignment, then the sums,
+ * with scratch of its own (psgd_kmeans_plan tells how much).
+ * psgd_kmeans_update_device makes the next centres from a step's output and the centres the step
+ * started from: c_j = sums[j] * (1.0 / counts[j]) where counts[j] > 0, else the old c_j (an empty cluster
+ * keeps its centre); d_moved[j] = ||c_new_j - c_old_j||^2. d_new_centres must not be d_centres. It reads
+ * no rows and needs no registered partition.
+ * Reproducibility: dense rows go through v_mfma_f64_16x16x4_f64 in both passes (assignment: M = rows,
+ * K = features, N = centres; sums: M = centres, N = features, K = rows, the A operand a one-hot of the
+ * assignments, so every product is 1.0 x or 0.0 x); no atomics; every output has the same bits from
+ * call to call, whatever the grid. CSR rows: assign, dist2, cost and counts have the same bits from call
+ * to call; the sums are added with fp64 atomics (one an entry) and repeat only up to their last bits.
+ * Errors: PSGD_EINVAL for a null ctx or pointer (dist2 / d_dist2 may be null) or k < 1;
+ * PSGD_EUNSUPPORTED for k > PSGD_KMEANS_MAX_K; PSGD_ESTATE when no partition is registered. A registry
+ * of empty partitions writes no assignment and returns a step of zeros.
+ * The calls only read the rows (any kind of registration). Like the scoring calls they wait for
+ * registration copies in flight, order themselves against an epoch running on another stream and leave
+ * the epoch state alone. The _device forms take device pointers and a stream (NULL: the context's);
+ * they wait once for their tile table to leave the host. */
+#define PSGD_KMEANS_MAX_K 256
+int32_t psgd_kmeans_assign(psgd_ctx* ctx, int32_t k, const double* centres, int32_t* assign, double* dist2);
+int32_t psgd_kmeans_assign_device(psgd_ctx* ctx, int32_t k, const double* d_centres, int32_t* d_assign, double* d_dist2,
+                                  void* stream);
+int32_t psgd_kmeans_step(psgd_ctx* ctx, int32_t k, const double* centres, double* out);
+int32_t psgd_kmeans_step_device(psgd_ctx* ctx, int32_t k, const double* d_centres, double* d_out, void* stream);
+int32_t psgd_kmeans_update_device(psgd_ctx* ctx, int32_t k, int32_t d, const double* d_centres, const double* d_step,
+                                  double* d_new_centres, double* d_moved, void* stream);
+
+/* How the k-means passes run rows of `layout` (0 dense, 1 CSR), `storage` (psgd_dtype) and d features
+ * against k centres when the rows are cut into total_tiles tiles (dense: 16 rows a tile, CSR 256, a
+ * partition's last tile short): host code, no device and no context. out[PSGD_KMEANS_PLAN_LEN] receives
+ *   [0] the path: 0 dense MFMA with C^T in LDS, 1 dense MFMA with C^T read through L2 (LDS while d
+ *       rounded up to whole steps x kpad doubles fit a CU's 160 KiB), 2 CSR with the sums' accumulators
+ *       in LDS (k d <= 6,144 doubles), 3 CSR with the sums added into global memory;
+ *   [1] dense: CB, the centre blocks of 16 of a chunk (1, 2, 4); CSR: centres a lane keeps;
+ *   [2] [3] dense sums: the rectangle of centre blocks x feature blocks a wave keeps (CSR 0);
+ *   [4] [5] dense sums: tiles a span and spans; CSR: the same of the merge of the tiles' costs;
+ *   [6] dense sums: items, spans x rectangles (CSR 0);
+ *   [7] bytes of scratch of a step, the assignments aside (bounded: [6] is capped);
+ *   [8] bytes of dynamic LDS of the assignment kernel (0 when C^T is read through L2);
+ *   [9] rows a tile;
+ *   [10] kpad = 16 ceil(k / 16);
+ *   [11] CSR assignment: lanes a row, the power of two >= k, 64 at most (dense 0).
+ * Errors: PSGD_EINVAL for a null out, an unknown layout or storage, d <= 0, k < 1 or total_tiles < 0;
+ * PSGD_EUNSUPPORTED for k > PSGD_KMEANS_MAX_K. */
+#define PSGD_KMEANS_PLAN_LEN 12
+int32_t psgd_kmeans_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t total_tiles, int64_t* out);
+
 /* One GradientDescent update from a psgd_gradient_sum result `sum` (d + 2 doubles):
  *   (w_out, *regval_out) = updater.compute(w, sum[0 .. d) / sum[d + 1], step_size, iteration, reg_param)
  * for the stateless updaters, MLlib's SimpleUpdater / SquaredL2Updater / L1Updater, with

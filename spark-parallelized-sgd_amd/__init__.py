@@ -19,6 +19,7 @@ from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine,
 from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradient_sum_multinomial, runMiniBatchSGD,
                                runMiniBatchSGDMultinomial)
 from .newton import HessianSum, Newton, hessian_sum, runNewton
+from .clustering import KMeans, KMeansModel, KMeansStep, kmeans_step
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
@@ -33,6 +34,7 @@ __all__ = [
     "GradientDescent", "runMiniBatchSGD", "gradient_sum", "GradientSum",
     "gradient_sum_multinomial", "runMiniBatchSGDMultinomial",
     "Newton", "runNewton", "hessian_sum", "HessianSum",
+    "KMeans", "KMeansModel", "KMeansStep", "kmeans_step",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
     "multiply", "computePrincipalComponents", "computeSVD", "PCA", "PCAModel",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",

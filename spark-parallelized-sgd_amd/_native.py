@@ -37,6 +37,8 @@ EXPORTED = (
     "psgd_gramian_weighted", "psgd_gramian_weighted_device", "psgd_local_rows",
     "psgd_row_curvature", "psgd_row_curvature_device",
     "psgd_project", "psgd_project_device", "psgd_project_plan",
+    "psgd_kmeans_assign", "psgd_kmeans_assign_device", "psgd_kmeans_step", "psgd_kmeans_step_device",
+    "psgd_kmeans_update_device", "psgd_kmeans_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
     "psgd_evaluate_multinomial", "psgd_evaluate_multinomial_device",
@@ -158,6 +160,12 @@ def lib():
             "psgd_project": ([vp, C.c_int64, C.c_int32, vp, vp], C.c_int32),
             "psgd_project_device": ([vp, C.c_int32, vp, C.c_int32, C.c_int64, vp, vp, vp], C.c_int32),
             "psgd_project_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
+            "psgd_kmeans_assign": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_kmeans_assign_device": ([vp, C.c_int32, vp, vp, vp, vp], C.c_int32),
+            "psgd_kmeans_step": ([vp, C.c_int32, vp, vp], C.c_int32),
+            "psgd_kmeans_step_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_kmeans_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_kmeans_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
             "psgd_gd_update": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, dp],
                                C.c_int32),
             "psgd_gd_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp,
@@ -271,6 +279,23 @@ def project_plan(layout: str, storage: str, d: int, k: int, max_nnz: int = 0) ->
     keys = ("path", "kpad", "rows_wave", "comp_blocks", "feature_chunk", "lds_bytes", "scratch_bytes", "row_lanes")
     plan = {k_: int(v) for k_, v in zip(keys, out)}
     plan["path"] = PROJECT_PATHS[plan["path"]]
+    return plan
+
+
+KMEANS_MAX_K = 256     # PSGD_KMEANS_MAX_K
+KMEANS_PATHS = ("dense_lds", "dense_l2", "csr_lds_sums", "csr_global_sums")
+
+
+def kmeans_plan(layout: str, storage: str, d: int, k: int, total_tiles: int) -> dict:
+    """How the k-means passes run rows of `layout` ("dense" / "csr") stored as `storage` ("f32" / "f64")
+    with d features against k centres, cut into total_tiles tiles (psgd_kmeans_plan: host code, no device)."""
+    out = (C.c_int64 * 12)()
+    check(lib().psgd_kmeans_plan({"dense": 0, "csr": 1}[layout], {"f64": 0, "f32": 1}[storage], int(d), int(k),
+                                 int(total_tiles), out))
+    keys = ("path", "centre_blocks", "gr", "gc", "span_tiles", "spans", "items", "scratch_bytes", "lds_bytes",
+            "tile_rows", "kpad", "row_lanes")
+    plan = {k_: int(v) for k_, v in zip(keys, out)}
+    plan["path"] = KMEANS_PATHS[plan["path"]]
     return plan
 
 
@@ -622,6 +647,38 @@ class Context:
         ls = np.ascontiguousarray(label_ptrs, dtype=np.uint64)
         check(self._L.psgd_project_device(self.handle, int(k), b_ptr, int(out_storage), int(ld_out), ys.ctypes.data,
                                           ls.ctypes.data, stream))
+
+    # k-means ------------------------------------------------------------------------------------
+    def kmeans_assign(self, centres, distances: bool = False):
+        """Host-pointer form (psgd_kmeans_assign): (assign int32 [local rows], dist2 or None)."""
+        import numpy as np
+        c = np.ascontiguousarray(centres, dtype=np.float64)
+        n = self.local_rows()
+        assign = np.zeros(max(n, 1), dtype=np.int32)
+        dist2 = np.zeros(max(n, 1), dtype=np.float64) if distances else None
+        check(self._L.psgd_kmeans_assign(self.handle, int(c.shape[0]), c.ctypes.data, assign.ctypes.data,
+                                         None if dist2 is None else dist2.ctypes.data))
+        return assign[:n], None if dist2 is None else dist2[:n]
+
+    def kmeans_assign_device(self, k: int, c_ptr, assign_ptr, dist2_ptr, stream=None):
+        """psgd_kmeans_assign_device: enqueued on `stream`; assign / dist2 (0: none) [local rows] on the device."""
+        check(self._L.psgd_kmeans_assign_device(self.handle, int(k), c_ptr, assign_ptr, dist2_ptr or None, stream))
+
+    def kmeans_step(self, centres):
+        """Host-pointer form (psgd_kmeans_step): {sums[k][d], counts[k], cost, n} as k (d + 1) + 2 doubles."""
+        import numpy as np
+        c = np.ascontiguousarray(centres, dtype=np.float64)
+        out = np.zeros(c.shape[0] * (c.shape[1] + 1) + 2, dtype=np.float64)
+        check(self._L.psgd_kmeans_step(self.handle, int(c.shape[0]), c.ctypes.data, out.ctypes.data))
+        return out
+
+    def kmeans_step_device(self, k: int, c_ptr, out_ptr, stream=None):
+        """psgd_kmeans_step_device: enqueued on `stream`; out[k (d + 1) + 2] on the device."""
+        check(self._L.psgd_kmeans_step_device(self.handle, int(k), c_ptr, out_ptr, stream))
+
+    def kmeans_update_device(self, k: int, d: int, c_ptr, step_ptr, new_ptr, moved_ptr, stream=None):
+        """psgd_kmeans_update_device: the next centres [k d] and moved [k] from a step's output."""
+        check(self._L.psgd_kmeans_update_device(self.handle, int(k), int(d), c_ptr, step_ptr, new_ptr, moved_ptr, stream))
 
     def transform_columns(self, shift, factor):
         """Host-pointer form (psgd_transform_columns): x = ((double)x - shift) * factor in place on

@@ -470,6 +470,9 @@ struct psgd_ctx {
     // staging of counts and nnz, and a compaction's table with the CSR tiles' sums
     DevBuf cidx, csel, stab;
     std::vector<int64_t> row_off;
+    // k-means (psgd_kmeans_*): a step's assignments, and the host-pointer forms' staging (the scratch
+    // is the Gramian's qrec, the tile table the compactions' stab)
+    DevBuf kassign, kio;
 };
 
 namespace {
@@ -843,7 +846,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
                           &ctx->qrec, &ctx->qio, &ctx->qomega,
                           &ctx->mscratch, &ctx->mio, &ctx->cidx, &ctx->csel, &ctx->stab,
-                          &ctx->watchdog})
+                          &ctx->kassign, &ctx->kio, &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
             if (ctx->ev_begin[k]) hipEventDestroy(ctx->ev_begin[k]);
@@ -3145,6 +3148,172 @@ int32_t psgd_project_plan(int32_t layout, int32_t storage, int32_t d, int32_t k,
     const psgd::ProjGeom gm = psgd::project_geometry(layout, storage == PSGD_F32 ? 1 : 0, d, k, max_nnz);
     const int64_t v[PSGD_PROJECT_PLAN_LEN] = {gm.path,   gm.kpad,      gm.rows_wave,     gm.cb,
                                               gm.fchunk, gm.lds_bytes, gm.scratch_bytes, gm.group};
+    std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
+// ---- Lloyd's iteration of k-means (kernels in psgd_kmeans.hip) ----
+// The same place in the context as the projection: score_prepare, the tile table in ctx->stab, the
+// scratch in ctx->qrec, a step's assignments in ctx->kassign, no epoch state touched.
+static int32_t kmeans_args(int32_t k) {
+    if (k < 1) return fail(PSGD_EINVAL, "k must be at least 1");
+    if (k > PSGD_KMEANS_MAX_K)
+        return fail(PSGD_EUNSUPPORTED, "k-means with k = " + std::to_string(k) + " centres exceeds the built maximum of " +
+                                           std::to_string(PSGD_KMEANS_MAX_K));
+    return PSGD_OK;
+}
+
+// An assignment (d_out null) or a step (d_assign / d_dist2 unused) on `st` (ctx->mu held, score_prepare done).
+static int32_t kmeans_enqueue(psgd_ctx* ctx, int32_t k, const double* d_C, int32_t* d_assign, double* d_dist2,
+                              double* d_out, hipStream_t st) {
+    const Part& first = ctx->parts.begin()->second;
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    const int tile_rows = first.layout == psgd::kCsr ? 256 : 16;
+    const size_t P = ctx->parts.size();
+    std::vector<psgd::KmPart> tab(P + 1);
+    int64_t tiles = 0, max_nnz = 0;
+    size_t c = 0;
+    for (auto& kv : ctx->parts) {
+        tab[c] = psgd::KmPart{tiles, ctx->row_off[c]};
+        tiles += (kv.second.n_rows + tile_rows - 1) / tile_rows;
+        max_nnz = std::max(max_nnz, kv.second.max_nnz);
+        ++c;
+    }
+    const int64_t n_rows = ctx->row_off.back();
+    tab[P] = psgd::KmPart{tiles, n_rows};
+    const psgd::KmGeom gm = psgd::kmeans_geometry(first.layout, storage, first.d, k, tiles, max_nnz);
+    HIP_TRY(ctx->qrec.ensure((size_t)(d_out ? gm.scratch_bytes : gm.assign_bytes) + sizeof(double)));
+    if (tiles > 0) {
+        HIP_TRY(ctx->stab.ensure(tab.size() * sizeof(psgd::KmPart)));
+        HIP_TRY(hipMemcpyAsync(ctx->stab.p, tab.data(), tab.size() * sizeof(psgd::KmPart), hipMemcpyHostToDevice, st));
+        // the table leaves a host vector of this call: wait for the copy
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    int e;
+    if (d_out) {
+        HIP_TRY(ctx->kassign.ensure((size_t)std::max<int64_t>(n_rows, 1) * sizeof(int32_t)));
+        e = psgd::launch_kmeans_step(ctx->descs.as<psgd::ChainDesc>(), ctx->stab.as<psgd::KmPart>(), (int)P, tiles, n_rows,
+                                     gm, storage, d_C, ctx->qrec.as<double>(), ctx->kassign.as<int32_t>(), d_out,
+                                     ctx->num_cus, st);
+    } else {
+        e = psgd::launch_kmeans_assign(ctx->descs.as<psgd::ChainDesc>(), ctx->stab.as<psgd::KmPart>(), (int)P, tiles, gm,
+                                       storage, d_C, ctx->qrec.as<double>(), d_assign, d_dist2, nullptr, ctx->num_cus, st);
+    }
+    if (e) return fail(PSGD_EDEVICE, std::string("k-means launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+static int32_t kmeans_device(psgd_ctx* ctx, int32_t k, const double* d_C, int32_t* d_assign, double* d_dist2,
+                             double* d_out, void* stream) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int32_t rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    return kmeans_enqueue(ctx, k, d_C, d_assign, d_dist2, d_out, st);
+}
+
+int32_t psgd_kmeans_assign_device(psgd_ctx* ctx, int32_t k, const double* d_centres, int32_t* d_assign, double* d_dist2,
+                                  void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_centres || !d_assign) return fail(PSGD_EINVAL, "d_centres/d_assign are null");
+    const int32_t rc = kmeans_args(k);
+    if (rc) return rc;
+    return kmeans_device(ctx, k, d_centres, d_assign, d_dist2, nullptr, stream);
+}
+
+int32_t psgd_kmeans_step_device(psgd_ctx* ctx, int32_t k, const double* d_centres, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_centres || !d_out) return fail(PSGD_EINVAL, "d_centres/d_out are null");
+    const int32_t rc = kmeans_args(k);
+    if (rc) return rc;
+    return kmeans_device(ctx, k, d_centres, nullptr, nullptr, d_out, stream);
+}
+
+// The host-pointer forms: the centres staged in, the results staged out through ctx->kio:
+// [centres k d | out k (d + 1) + 2 or dist2 n | assign n].
+static int32_t kmeans_host(psgd_ctx* ctx, int32_t k, const double* centres, int32_t* assign, double* dist2, double* out) {
+    size_t n = 0, kd = 0, len = 0;
+    double *d_C = nullptr, *d_res = nullptr;
+    int32_t* d_assign = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        const size_t d = (size_t)ctx->parts.begin()->second.d;
+        for (auto& kv : ctx->parts) n += (size_t)kv.second.n_rows;
+        kd = (size_t)k * d;
+        len = out ? kd + (size_t)k + 2 : std::max<size_t>(n, 1);
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        const int32_t rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->kio.ensure((kd + len) * sizeof(double) + std::max<size_t>(n, 1) * sizeof(int32_t)));
+        d_C = ctx->kio.as<double>();
+        d_res = d_C + kd;
+        d_assign = reinterpret_cast<int32_t*>(d_res + len);
+        HIP_TRY(hipMemcpyAsync(d_C, centres, kd * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        // the caller's array is pageable in general: the copy has left it when this returns
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    const int32_t rc = out ? kmeans_device(ctx, k, d_C, nullptr, nullptr, d_res, ctx->stream)
+                           : kmeans_device(ctx, k, d_C, d_assign, dist2 ? d_res : nullptr, nullptr, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    if (out) {
+        HIP_TRY(hipMemcpyAsync(out, d_res, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    } else if (n > 0) {
+        HIP_TRY(hipMemcpyAsync(assign, d_assign, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (dist2) HIP_TRY(hipMemcpyAsync(dist2, d_res, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_kmeans_assign(psgd_ctx* ctx, int32_t k, const double* centres, int32_t* assign, double* dist2) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!centres || !assign) return fail(PSGD_EINVAL, "centres/assign are null");
+    const int32_t rc = kmeans_args(k);
+    if (rc) return rc;
+    return kmeans_host(ctx, k, centres, assign, dist2, nullptr);
+}
+
+int32_t psgd_kmeans_step(psgd_ctx* ctx, int32_t k, const double* centres, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!centres || !out) return fail(PSGD_EINVAL, "centres/out are null");
+    const int32_t rc = kmeans_args(k);
+    if (rc) return rc;
+    return kmeans_host(ctx, k, centres, nullptr, nullptr, out);
+}
+
+int32_t psgd_kmeans_update_device(psgd_ctx* ctx, int32_t k, int32_t d, const double* d_centres, const double* d_step,
+                                  double* d_new_centres, double* d_moved, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_centres || !d_step || !d_new_centres || !d_moved)
+        return fail(PSGD_EINVAL, "d_centres/d_step/d_new_centres/d_moved are null");
+    if (d < 1) return fail(PSGD_EINVAL, "d must be positive");
+    if (d_new_centres == d_centres) return fail(PSGD_EINVAL, "d_new_centres must not be d_centres");
+    const int32_t rc = kmeans_args(k);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int e = psgd::launch_kmeans_update(k, d, d_centres, d_step, d_new_centres, d_moved, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("k-means update launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_kmeans_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t total_tiles, int64_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (layout != psgd::kDense && layout != psgd::kCsr) return fail(PSGD_EINVAL, "unknown layout " + std::to_string(layout));
+    if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
+    if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
+    if (total_tiles < 0) return fail(PSGD_EINVAL, "total_tiles must be >= 0");
+    const int32_t rc = kmeans_args(k);
+    if (rc) return rc;
+    const psgd::KmGeom gm = psgd::kmeans_geometry(layout, storage == PSGD_F32 ? 1 : 0, d, k, total_tiles, 0);
+    const int64_t v[PSGD_KMEANS_PLAN_LEN] = {gm.path, gm.cb,      gm.gr,      gm.gc,           gm.span,     gm.n_spans,
+                                             gm.n_items, gm.scratch_bytes, gm.lds_bytes, gm.tile_rows, gm.kpad, gm.group};
     std::memcpy(out, v, sizeof v);
     return PSGD_OK;
 }

@@ -407,6 +407,49 @@ int launch_project(const ChainDesc* descs, const ProjPart* tab, int n_parts, int
                    int storage, int out_storage, const double* B, double* Bp, int64_t ld_out, int num_cus,
                    hipStream_t st);
 
+// ---- Lloyd's iteration of k-means (psgd_kmeans.hip: psgd_kmeans_assign / psgd_kmeans_step) ----
+// The plan of a call: host code, no device (psgd_kmeans_plan reports it).
+enum KmPath { kKmDenseLds = 0, kKmDenseL2 = 1, kKmCsrLdsSums = 2, kKmCsrGlobalSums = 3 };
+constexpr int kKmeansMaxK = 256;
+struct KmGeom {
+    int32_t d, k;
+    int32_t kpad, nb;        // 16 ceil(k / 16) centres of the widened C^T, their blocks of 16
+    int32_t path;            // KmPath
+    int32_t cb;              // dense assign: centre blocks of a chunk (1, 2, 4); CSR: centres a lane keeps
+    int32_t dpad;            // dense: d rounded up to whole steps of four 16-byte vectors
+    int32_t group;           // CSR assign: lanes a row (the power of two >= k, at most 64)
+    int32_t sgroup;          // CSR sums: lanes across a row's entries (16, 32, 64 by the longest row)
+    int32_t clds;            // C^T is staged in LDS by the assign kernel
+    int32_t tile_rows;       // rows a tile: dense 16, CSR 256
+    int32_t gr, gc;          // dense sums: centre blocks x feature blocks a wave keeps
+    int32_t nbf, nrg, ncg;   // dense sums: feature blocks of [x, 1], rectangle rows and columns
+    int64_t span, n_spans;   // dense sums: tiles a span, spans; CSR: the merge of the tiles' costs
+    int64_t n_items;         // dense sums: spans x rectangles
+    int64_t lds_bytes;       // dynamic LDS of the assign launch (dense, CSR) -- the CSR sums' is k (d + 1) doubles
+    int64_t pack_doubles;    // dense: C^T in the MFMA operands' order, then cn [kpad]; CSR: cn [kpad]
+    int64_t assign_bytes;    // scratch of an assign call: pack, the tiles' costs and their merge
+    int64_t scratch_bytes;   // scratch of a step but the assignments: the above, then the sums' records / counts
+};
+KmGeom kmeans_geometry(int layout, int storage, int d, int k, int64_t n_tiles, int64_t max_nnz);
+// One partition of a k-means pass: its first tile (tiles of gm.tile_rows rows numbered across the
+// partitions in partition-index order) and its first row in local row order; entry n_parts closes the list.
+struct KmPart {
+    int64_t tile0;
+    int64_t row0;
+};
+// assign [rows] / dist2 [rows] (nullable) in local row order at centres C [k * d] row-major; scratch is
+// gm.scratch_bytes. cost (nullable): the sum of dist2 in tile order, one double.
+int launch_kmeans_assign(const ChainDesc* descs, const KmPart* tab, int n_parts, int64_t n_tiles, const KmGeom& gm,
+                         int storage, const double* C, double* scratch, int32_t* assign, double* dist2, double* cost,
+                         int num_cus, hipStream_t st);
+// out[k (d + 1) + 2] = {sums[k][d], counts[k], cost, n}: assign, then the centre sums.
+int launch_kmeans_step(const ChainDesc* descs, const KmPart* tab, int n_parts, int64_t n_tiles, int64_t n_rows,
+                       const KmGeom& gm, int storage, const double* C, double* scratch, int32_t* assign, double* out,
+                       int num_cus, hipStream_t st);
+// c_new[j] = counts[j] > 0 ? sums[j] * (1 / counts[j]) : c[j]; moved[j] = ||c_new[j] - c[j]||^2. c_new may not be c.
+int launch_kmeans_update(int k, int d, const double* C, const double* step, double* c_new, double* moved,
+                         hipStream_t st);
+
 // w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
 // the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
 int64_t gd_update_blocks(int d);

@@ -789,6 +789,126 @@ class HipEngine(ShardedEngine):
                                lambda w_ptr, out: self.ctx.row_curvature_device(
                                    kind, w_ptr, out, self.stream.cuda_stream), local=True)[: self.local_rows()]
 
+    # k-means (psgd_kmeans_*_device; clustering.py) -----------------------------------------------
+    def _centres(self, centres):
+        """centres (host array or device tensor, [k, num_features]) as a contiguous f64 device tensor
+        (self.stream is current)."""
+        nf = self._data.num_features
+        if self.torch.is_tensor(centres):
+            c = centres.detach().to(device=self.dev, dtype=self.torch.float64).contiguous()
+        else:
+            c = self.torch.from_numpy(np.ascontiguousarray(centres, dtype=np.float64)).to(self.dev)
+        if c.dim() != 2 or c.shape[1] != nf or not 1 <= c.shape[0] <= N.KMEANS_MAX_K:
+            raise IllegalArgumentException(
+                f"requirement failed: the centres must be [k, {nf}] with 1 <= k <= {N.KMEANS_MAX_K} "
+                f"(got shape {tuple(c.shape)})")
+        return c
+
+    def kmeans_assign(self, centres, distances: bool = False):
+        """(assign, dist2) of every row of this rank's partitions at `centres` [k, num_features] (a host
+        array or a device tensor): device tensors of local_rows() int32 / doubles in partition and
+        iterator order (include/psgd.h has the semantics; dist2 is None unless `distances`). The rows
+        are this rank's own, so the ranks exchange nothing here."""
+        torch = self.torch
+        n = self.local_rows()
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            c = self._centres(centres)
+            assign = torch.zeros(max(n, 1), dtype=torch.int32, device=self.dev)
+            dist2 = torch.zeros(max(n, 1), dtype=torch.float64, device=self.dev) if distances else None
+            if self.n_local > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    self.ctx.kmeans_assign_device(c.shape[0], c.data_ptr(), assign.data_ptr(),
+                                                  0 if dist2 is None else dist2.data_ptr(), self.stream.cuda_stream)
+            keep = torch.cuda.Event()
+            keep.record(self.stream)
+        caller.wait_stream(self.stream)
+        for t in (assign, dist2):
+            if t is not None:
+                t.record_stream(caller)
+        keep.synchronize()   # c may be a temporary of this call
+        return assign[:n], None if dist2 is None else dist2[:n]
+
+    def kmeans_step(self, centres):
+        """{sums[k][d], counts[k], cost, n} of one Lloyd step at `centres` over every row of the data, on
+        all ranks, as a device tensor of k (d + 1) + 2 doubles (psgd_kmeans_step_device). The ranks
+        all-gather their steps and every rank adds them in rank order, as gradient_sum does."""
+        self.stream.wait_stream(self.torch.cuda.current_stream(self.dev))
+        with self.torch.cuda.stream(self.stream):
+            c = self._centres(centres)   # (validated here: k comes from the converted tensor)
+        k, nf = int(c.shape[0]), self._data.num_features
+        return self._batch_sum(k * (nf + 1) + 2, self._centres, c,
+                               lambda c_ptr, out: self.ctx.kmeans_step_device(k, c_ptr, out, self.stream.cuda_stream))
+
+    def kmeans_update(self, centres_dev, step):
+        """(new centres [k, d], moved [k]) from a kmeans_step result and the device centres it started
+        from (psgd_kmeans_update_device): an empty cluster keeps its centre."""
+        torch = self.torch
+        self.stream.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(self.stream):
+            c = self._centres(centres_dev)
+            k, d = int(c.shape[0]), int(c.shape[1])
+            new = torch.empty_like(c)
+            moved = torch.empty(k, dtype=torch.float64, device=self.dev)
+            self.ctx.kmeans_update_device(k, d, c.data_ptr(), step.data_ptr(), new.data_ptr(), moved.data_ptr(),
+                                          self.stream.cuda_stream)
+        self.stream.synchronize()
+        return new, moved
+
+    def registered_rows(self, positions) -> np.ndarray:
+        """The rows at the global positions `positions` (partition order, then iterator order) as the
+        engine registered them -- a column_transform applied the way the device applies it, CSR rows
+        densified -- as a [len(positions), num_features] float64 host array, the same on every rank:
+        each rank fills the rows it owns into zeros and the arrays are added in rank order (exact:
+        every row has one owner)."""
+        data, nf = self._data, self._data.num_features
+        counts = getattr(data, "partition_counts", None)
+        if counts is None:
+            counts = [q.n_rows for q in data.partitions]
+        starts = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+        out = np.zeros((len(positions), nf), dtype=np.float64)
+        tr = getattr(data, "column_transform", None)
+        for t, g in enumerate(positions):
+            p = int(np.searchsorted(starts, g, side="right")) - 1
+            if not self.lo <= p < self.hi:
+                continue
+            part, i = data.partitions[p], int(g - starts[p])
+            if isinstance(part, DevicePartition):
+                row = part.x[i, :nf].cpu().numpy()
+            elif isinstance(part, (CsrPartition, DeviceCsrPartition)):
+                host = (lambda v: v.cpu().numpy()) if isinstance(part, DeviceCsrPartition) else np.asarray
+                a, b = (int(v) for v in host(part.row_ptr[i:i + 2]))
+                row = np.zeros(nf, dtype=host(part.val[:0]).dtype)
+                row[host(part.col[a:b])] = host(part.val[a:b])
+            else:
+                row = part.x[i]
+            if tr is not None:   # psgd_transform_columns: ((double)x - shift) * factor, rounded to the storage
+                shift, factor = tr
+                wide = row.astype(np.float64)
+                row = ((wide - shift if shift is not None else wide) * factor).astype(row.dtype)
+            out[t] = row
+        if self.world > 1:
+            torch = self.torch
+            with torch.cuda.stream(self.stream):
+                buf = torch.from_numpy(out.reshape(-1).copy()).to(self.dev)
+                out = self._rank_sum(buf, buf.numel()).cpu().numpy().reshape(out.shape)
+        return out
+
+    def _rank_sum(self, buf, width: int):
+        """The ranks' `width` doubles all-gathered (the backends of exchange()) and added in rank order
+        (merge_gradient_sums: a loop, not a tree): the same bits on every rank (self.stream is current)."""
+        torch = self.torch
+        import torch.distributed as dist
+        out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
+        if dist.get_backend() == "gloo":
+            dist.all_gather(list(out.view(self.world, width).unbind(0)), buf)
+        else:
+            dist.all_gather_into_tensor(out, buf)
+        return merge_gradient_sums(out.view(self.world, width))
+
     def _batch_sum(self, width: int, to_device, w, call, local: bool = False):
         """call(w_ptr, out_ptr) over this rank's partitions into `width` zeroed doubles, then the ranks'
         all-gather and the rank-order sum (not for a `local` result, which is this rank's alone).
@@ -806,13 +926,7 @@ class HipEngine(ShardedEngine):
                         self._register(self._data)
                     call(None if w_dev is None else w_dev.data_ptr(), buf.data_ptr())
             if self.world > 1 and not local:
-                import torch.distributed as dist
-                out = torch.empty(self.world * width, dtype=torch.float64, device=self.dev)
-                if dist.get_backend() == "gloo":
-                    dist.all_gather(list(out.view(self.world, width).unbind(0)), buf)
-                else:
-                    dist.all_gather_into_tensor(out, buf)
-                buf = merge_gradient_sums(out.view(self.world, width))
+                buf = self._rank_sum(buf, width)
             keep = torch.cuda.Event()
             keep.record(self.stream)
         caller.wait_stream(self.stream)
