@@ -582,6 +582,67 @@ int32_t psgd_kmeans_update_device(psgd_ctx* ctx, int32_t k, int32_t d, const dou
 #define PSGD_KMEANS_PLAN_LEN 12
 int32_t psgd_kmeans_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t total_tiles, int64_t* out);
 
+/* One EM step of a Gaussian mixture over every registered row -- the passes behind MLlib 1.6.1's
+ * GaussianMixture and GaussianMixtureModel.predictSoft. Dense rows only. A model is k components
+ * (w_j, mu_j, Sigma_j), 1 <= k <= PSGD_GMM_MAX_K, over d <= PSGD_GMM_MAX_D features. The host prepares,
+ * in fp64, MultivariateGaussian's constants: Sigma_j = U diag(s) U^T, tol = EPS d max(s) with EPS = 2^-52,
+ * R_j = diag(s_pinv^(1/2)) U^T with zero rows where s <= tol, u_j = -(d ln 2 pi + sum_{s > tol} ln s) / 2.
+ * A call receives
+ *   A: k * d * d doubles, A_j[i][c] = R_j[c][i];   b: k * d doubles, b_j = R_j mu_j;
+ *   c: k doubles, c_j = ln w_j + u_j, finite.
+ * All arithmetic is fp64 whatever the storage. For a row x: v_jc = -b_j[c] + sum_i x_i A_j[i][c] (one fma
+ * chain along the features that starts at -b_j[c]); q_j = sum_c v_jc^2, the Mahalanobis form (its order:
+ * a lane's columns c = m, m + 16, .. ascending with fma, then the 16 lanes m by a fixed butterfly);
+ * p_j = EPS + exp(c_j - q_j / 2), MLlib's EPSILON + w_j pdf_j(x); P = sum_j p_j in ascending j;
+ * r_j = p_j / P; the row adds ln P to the log-likelihood (rows in tile order). A row far from every
+ * component has r_j = 1 / k and adds ln(k EPS). NaN and Inf are outside the contract. The labels are not
+ * read; the pad columns of a zero-copy row (ld > d) never reach the arithmetic.
+ * psgd_gmm_responsibilities writes resp[r][j] (psgd_local_rows x k doubles, row-major, local row order:
+ * partition-index order, then iterator order), q[r][j] in the same shape (nullable) and *loglik.
+ * psgd_gmm_moments_device returns the moments of caller-given responsibilities d_resp (the same shape;
+ * any finite values, 0 and negatives included, as for psgd_gramian_weighted): k (d + 1)^2 doubles,
+ * S_j = sum_rows r_j z z^T with z = [x, 1], row-major, both triangles: sum r x x^T = S_j[:d, :d],
+ * sum r x = S_j[:d, d], sum r = S_j[d][d]. The A operand of its MFMAs is z * r_j (one rounding), the B
+ * operand z: S_j == S_j^T bit for bit (the lower triangle is a copy of the upper).
+ * psgd_gmm_step runs both passes with the responsibilities in scratch of its own (psgd_gmm_plan tells how
+ * much) and returns k (d + 1)^2 + 2 doubles: the S_j, the log-likelihood, the row count.
+ * Reproducibility: both passes go through v_mfma_f64_16x16x4_f64 (E-step: M = rows, K = features, N = the
+ * components' columns side by side; moments: M = N = the columns of z, K = rows); no atomics; every
+ * output has the same bits from call to call, whatever the grid.
+ * Errors: PSGD_EINVAL for a null ctx or pointer (q / d_q may be null) or k < 1; PSGD_EUNSUPPORTED for
+ * k > PSGD_GMM_MAX_K, d > PSGD_GMM_MAX_D or CSR rows; PSGD_ESTATE when no partition is registered. A
+ * registry of empty partitions writes no responsibility and returns zeros.
+ * The calls only read the rows (any kind of registration). Like the k-means calls they wait for
+ * registration copies in flight, order themselves against an epoch running on another stream and leave
+ * the epoch state alone. The _device forms take device pointers and a stream (NULL: the context's);
+ * they wait once for their tile table to leave the host. */
+#define PSGD_GMM_MAX_K 256
+#define PSGD_GMM_MAX_D 256
+int32_t psgd_gmm_responsibilities(psgd_ctx* ctx, int32_t k, const double* A, const double* b, const double* c, double* resp,
+                                  double* q, double* loglik);
+int32_t psgd_gmm_responsibilities_device(psgd_ctx* ctx, int32_t k, const double* d_A, const double* d_b, const double* d_c,
+                                         double* d_resp, double* d_q, double* d_loglik, void* stream);
+int32_t psgd_gmm_moments_device(psgd_ctx* ctx, int32_t k, const double* d_resp, double* d_out, void* stream);
+int32_t psgd_gmm_step(psgd_ctx* ctx, int32_t k, const double* A, const double* b, const double* c, double* out);
+int32_t psgd_gmm_step_device(psgd_ctx* ctx, int32_t k, const double* d_A, const double* d_b, const double* d_c,
+                             double* d_out, void* stream);
+
+/* How the mixture passes run rows of `layout` (0 dense), `storage` (psgd_dtype) and d features against k
+ * components when the rows are cut into total_tiles tiles of 16 rows (a partition's last tile short): host
+ * code, no device and no context. out[PSGD_GMM_PLAN_LEN] receives
+ *   [0] the path: 0 the packed operands (d rounded up to whole steps x 16 k db doubles) in LDS in front of
+ *       the waves' staging (8 x (16 k + 16) doubles) while both fit a CU's 160 KiB, 1 read through L2;
+ *   [1] CB, the column blocks of 16 of a chunk (1, 2, 4);   [2] db = ceil(d / 16), the blocks a component;
+ *   [3] [4] moments: the rectangle of blocks x blocks of S_j a wave keeps;
+ *   [5] [6] moments: tiles a span and spans;   [7] moments: items, spans x k x rectangles;
+ *   [8] bytes of scratch of a call, the responsibilities aside (bounded: [7] is capped);
+ *   [9] the same with a step's responsibilities, total_tiles x 16 x k doubles at most;
+ *   [10] bytes of dynamic LDS of the E-step kernel;   [11] rows a tile;   [12] waves of its workgroup.
+ * Errors: PSGD_EINVAL for a null out, an unknown layout or storage, d <= 0, k < 1 or total_tiles < 0;
+ * PSGD_EUNSUPPORTED for k > PSGD_GMM_MAX_K, d > PSGD_GMM_MAX_D or layout 1 (CSR). */
+#define PSGD_GMM_PLAN_LEN 13
+int32_t psgd_gmm_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t total_tiles, int64_t* out);
+
 /* One GradientDescent update from a psgd_gradient_sum result `sum` (d + 2 doubles):
  *   (w_out, *regval_out) = updater.compute(w, sum[0 .. d) / sum[d + 1], step_size, iteration, reg_param)
  * for the stateless updaters, MLlib's SimpleUpdater / SquaredL2Updater / L1Updater, with

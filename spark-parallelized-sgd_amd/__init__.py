@@ -19,13 +19,14 @@ from .optimization import (ColumnStats, DriverCheckpoint, Evaluation, HipEngine,
 from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradient_sum_multinomial, runMiniBatchSGD,
                                runMiniBatchSGDMultinomial)
 from .newton import HessianSum, Newton, hessian_sum, runNewton
-from .clustering import KMeans, KMeansModel, KMeansStep, kmeans_step
+from .clustering import (GaussianMixture, GaussianMixtureModel, GaussianMixtureStep, KMeans, KMeansModel, KMeansStep,
+                         gmm_step, kmeans_step)
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
 from .split import kFold, randomSplit
-from .stat import (Gramian, computePrincipalComponents, computeSVD, corr, covariance, gramian, multiply,
-                   normal_equations)
+from .stat import (Gramian, MultivariateGaussian, computePrincipalComponents, computeSVD, corr, covariance, gramian,
+                   multiply, normal_equations)
 from .util import loadLibSVMFile
 
 __all__ = [
@@ -35,6 +36,7 @@ __all__ = [
     "gradient_sum_multinomial", "runMiniBatchSGDMultinomial",
     "Newton", "runNewton", "hessian_sum", "HessianSum",
     "KMeans", "KMeansModel", "KMeansStep", "kmeans_step",
+    "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureStep", "gmm_step", "MultivariateGaussian",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
     "multiply", "computePrincipalComponents", "computeSVD", "PCA", "PCAModel",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",

@@ -39,6 +39,8 @@ EXPORTED = (
     "psgd_project", "psgd_project_device", "psgd_project_plan",
     "psgd_kmeans_assign", "psgd_kmeans_assign_device", "psgd_kmeans_step", "psgd_kmeans_step_device",
     "psgd_kmeans_update_device", "psgd_kmeans_plan",
+    "psgd_gmm_responsibilities", "psgd_gmm_responsibilities_device", "psgd_gmm_moments_device",
+    "psgd_gmm_step", "psgd_gmm_step_device", "psgd_gmm_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
     "psgd_metrics_sort_tile",
     "psgd_evaluate_multinomial", "psgd_evaluate_multinomial_device",
@@ -166,6 +168,12 @@ def lib():
             "psgd_kmeans_step_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
             "psgd_kmeans_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_kmeans_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
+            "psgd_gmm_responsibilities": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_gmm_responsibilities_device": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_gmm_moments_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_gmm_step": ([vp, C.c_int32, vp, vp, vp, vp], C.c_int32),
+            "psgd_gmm_step_device": ([vp, C.c_int32, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_gmm_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
             "psgd_gd_update": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, dp],
                                C.c_int32),
             "psgd_gd_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, C.c_double, C.c_int32, C.c_double, vp, vp,
@@ -296,6 +304,25 @@ def kmeans_plan(layout: str, storage: str, d: int, k: int, total_tiles: int) -> 
             "tile_rows", "kpad", "row_lanes")
     plan = {k_: int(v) for k_, v in zip(keys, out)}
     plan["path"] = KMEANS_PATHS[plan["path"]]
+    return plan
+
+
+GMM_MAX_K = 256     # PSGD_GMM_MAX_K
+GMM_MAX_D = 256     # PSGD_GMM_MAX_D
+GMM_PATHS = ("dense_lds", "dense_l2")
+
+
+def gmm_plan(layout: str, storage: str, d: int, k: int, total_tiles: int) -> dict:
+    """How the Gaussian mixture's passes run rows of `layout` ("dense"; "csr" is refused) stored as `storage`
+    ("f32" / "f64") with d features against k components, cut into total_tiles tiles (psgd_gmm_plan: host
+    code, no device)."""
+    out = (C.c_int64 * 13)()
+    check(lib().psgd_gmm_plan({"dense": 0, "csr": 1}[layout], {"f64": 0, "f32": 1}[storage], int(d), int(k),
+                              int(total_tiles), out))
+    keys = ("path", "chunk_blocks", "component_blocks", "gr", "gc", "span_tiles", "spans", "items", "scratch_bytes",
+            "scratch_bytes_with_resp", "lds_bytes", "tile_rows", "waves")
+    plan = {k_: int(v) for k_, v in zip(keys, out)}
+    plan["path"] = GMM_PATHS[plan["path"]]
     return plan
 
 
@@ -679,6 +706,43 @@ class Context:
     def kmeans_update_device(self, k: int, d: int, c_ptr, step_ptr, new_ptr, moved_ptr, stream=None):
         """psgd_kmeans_update_device: the next centres [k d] and moved [k] from a step's output."""
         check(self._L.psgd_kmeans_update_device(self.handle, int(k), int(d), c_ptr, step_ptr, new_ptr, moved_ptr, stream))
+
+    # Gaussian mixture ---------------------------------------------------------------------------
+    def gmm_responsibilities(self, A, b, c, mahalanobis: bool = False):
+        """Host-pointer form (psgd_gmm_responsibilities) at A [k, d, d], b [k, d], c [k]:
+        (resp [local rows, k], loglik, q or None)."""
+        import numpy as np
+        A, b, c = (np.ascontiguousarray(v, dtype=np.float64) for v in (A, b, c))
+        k, n = int(c.shape[0]), self.local_rows()
+        resp = np.zeros((max(n, 1), k), dtype=np.float64)
+        q = np.zeros((max(n, 1), k), dtype=np.float64) if mahalanobis else None
+        ll = np.zeros(1, dtype=np.float64)
+        check(self._L.psgd_gmm_responsibilities(self.handle, k, A.ctypes.data, b.ctypes.data, c.ctypes.data,
+                                                resp.ctypes.data, None if q is None else q.ctypes.data, ll.ctypes.data))
+        return resp[:n], float(ll[0]), None if q is None else q[:n]
+
+    def gmm_responsibilities_device(self, k: int, a_ptr, b_ptr, c_ptr, resp_ptr, q_ptr, ll_ptr, stream=None):
+        """psgd_gmm_responsibilities_device: enqueued on `stream`; resp / q (0: none) [local rows, k] and
+        loglik [1] on the device."""
+        check(self._L.psgd_gmm_responsibilities_device(self.handle, int(k), a_ptr, b_ptr, c_ptr, resp_ptr, q_ptr or None,
+                                                       ll_ptr, stream))
+
+    def gmm_moments_device(self, k: int, resp_ptr, out_ptr, stream=None):
+        """psgd_gmm_moments_device: out[k (d + 1)^2] from resp [local rows, k], both on the device."""
+        check(self._L.psgd_gmm_moments_device(self.handle, int(k), resp_ptr, out_ptr, stream))
+
+    def gmm_step(self, A, b, c):
+        """Host-pointer form (psgd_gmm_step): {S[k][d + 1][d + 1], loglik, n} as k (d + 1)^2 + 2 doubles."""
+        import numpy as np
+        A, b, c = (np.ascontiguousarray(v, dtype=np.float64) for v in (A, b, c))
+        k, d = int(b.shape[0]), int(b.shape[1])
+        out = np.zeros(k * (d + 1) * (d + 1) + 2, dtype=np.float64)
+        check(self._L.psgd_gmm_step(self.handle, k, A.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data))
+        return out
+
+    def gmm_step_device(self, k: int, a_ptr, b_ptr, c_ptr, out_ptr, stream=None):
+        """psgd_gmm_step_device: enqueued on `stream`; out[k (d + 1)^2 + 2] on the device."""
+        check(self._L.psgd_gmm_step_device(self.handle, int(k), a_ptr, b_ptr, c_ptr, out_ptr, stream))
 
     def transform_columns(self, shift, factor):
         """Host-pointer form (psgd_transform_columns): x = ((double)x - shift) * factor in place on

@@ -473,6 +473,9 @@ struct psgd_ctx {
     // k-means (psgd_kmeans_*): a step's assignments, and the host-pointer forms' staging (the scratch
     // is the Gramian's qrec, the tile table the compactions' stab)
     DevBuf kassign, kio;
+    // Gaussian mixture (psgd_gmm_*): a step's responsibilities, and the host-pointer forms' staging (the
+    // scratch is the Gramian's qrec, the tile table the compactions' stab)
+    DevBuf mixresp, mixio;
 };
 
 namespace {
@@ -846,7 +849,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
                           &ctx->qrec, &ctx->qio, &ctx->qomega,
                           &ctx->mscratch, &ctx->mio, &ctx->cidx, &ctx->csel, &ctx->stab,
-                          &ctx->kassign, &ctx->kio, &ctx->watchdog})
+                          &ctx->kassign, &ctx->kio, &ctx->mixresp, &ctx->mixio, &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
             if (ctx->ev_begin[k]) hipEventDestroy(ctx->ev_begin[k]);
@@ -3314,6 +3317,198 @@ int32_t psgd_kmeans_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, 
     const psgd::KmGeom gm = psgd::kmeans_geometry(layout, storage == PSGD_F32 ? 1 : 0, d, k, total_tiles, 0);
     const int64_t v[PSGD_KMEANS_PLAN_LEN] = {gm.path, gm.cb,      gm.gr,      gm.gc,           gm.span,     gm.n_spans,
                                              gm.n_items, gm.scratch_bytes, gm.lds_bytes, gm.tile_rows, gm.kpad, gm.group};
+    std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
+// ---- One EM step of a Gaussian mixture (kernels in psgd_gmm.hip) ----
+// The same place in the context as k-means: score_prepare, the tile table in ctx->stab, the scratch in
+// ctx->qrec, a step's responsibilities in ctx->mixresp, no epoch state touched.
+static int32_t gmm_args(int32_t k) {
+    if (k < 1) return fail(PSGD_EINVAL, "k must be at least 1");
+    if (k > PSGD_GMM_MAX_K)
+        return fail(PSGD_EUNSUPPORTED, "a mixture of k = " + std::to_string(k) + " components exceeds the built maximum of " +
+                                           std::to_string(PSGD_GMM_MAX_K));
+    return PSGD_OK;
+}
+
+static int32_t gmm_rows(int32_t layout, int32_t d) {
+    if (layout == psgd::kCsr) return fail(PSGD_EUNSUPPORTED, "the Gaussian mixture needs dense rows (the partitions are CSR)");
+    if (d > PSGD_GMM_MAX_D)
+        return fail(PSGD_EUNSUPPORTED, "a mixture over d = " + std::to_string(d) + " features exceeds the built maximum of " +
+                                           std::to_string(PSGD_GMM_MAX_D));
+    return PSGD_OK;
+}
+
+// What a call runs: the E-step alone (d_resp, d_q nullable, d_ll out), the moments of d_resp (d_out), or a
+// step (d_out; the responsibilities in ctx->mixresp).
+enum GmmMode { kGmmResp = 0, kGmmMoments = 1, kGmmStep = 2 };
+
+// On `st` (ctx->mu held, score_prepare done).
+static int32_t gmm_enqueue(psgd_ctx* ctx, int mode, int32_t k, const double* d_A, const double* d_b, const double* d_c,
+                           double* d_resp, double* d_q, double* d_ll, double* d_out, hipStream_t st) {
+    const Part& first = ctx->parts.begin()->second;
+    const int32_t rc = gmm_rows(first.layout, first.d);
+    if (rc) return rc;
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    const size_t P = ctx->parts.size();
+    std::vector<psgd::KmPart> tab(P + 1);
+    int64_t tiles = 0;
+    size_t c = 0;
+    for (auto& kv : ctx->parts) {
+        tab[c] = psgd::KmPart{tiles, ctx->row_off[c]};
+        tiles += (kv.second.n_rows + 15) / 16;
+        ++c;
+    }
+    const int64_t n_rows = ctx->row_off.back();
+    tab[P] = psgd::KmPart{tiles, n_rows};
+    const psgd::GmmGeom gm = psgd::gmm_geometry(storage, first.d, k, tiles);
+    HIP_TRY(ctx->qrec.ensure((size_t)gm.scratch_bytes + sizeof(double)));
+    if (tiles > 0) {
+        HIP_TRY(ctx->stab.ensure(tab.size() * sizeof(psgd::KmPart)));
+        HIP_TRY(hipMemcpyAsync(ctx->stab.p, tab.data(), tab.size() * sizeof(psgd::KmPart), hipMemcpyHostToDevice, st));
+        // the table leaves a host vector of this call: wait for the copy
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const psgd::ChainDesc* descs = ctx->descs.as<psgd::ChainDesc>();
+    const psgd::KmPart* d_tab = ctx->stab.as<psgd::KmPart>();
+    int e;
+    if (mode == kGmmResp) {
+        e = psgd::launch_gmm_estep(descs, d_tab, (int)P, tiles, gm, storage, d_A, d_b, d_c, ctx->qrec.as<double>(), d_resp,
+                                   d_q, d_ll, ctx->num_cus, st);
+    } else if (mode == kGmmMoments) {
+        e = psgd::launch_gmm_moments(descs, d_tab, (int)P, tiles, gm, storage, d_resp, ctx->qrec.as<double>(), d_out, st);
+    } else {
+        HIP_TRY(ctx->mixresp.ensure((size_t)std::max<int64_t>(n_rows, 1) * (size_t)k * sizeof(double)));
+        e = psgd::launch_gmm_step(descs, d_tab, (int)P, tiles, n_rows, gm, storage, d_A, d_b, d_c, ctx->qrec.as<double>(),
+                                  ctx->mixresp.as<double>(), d_out, ctx->num_cus, st);
+    }
+    if (e) return fail(PSGD_EDEVICE, std::string("Gaussian mixture launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+static int32_t gmm_device(psgd_ctx* ctx, int mode, int32_t k, const double* d_A, const double* d_b, const double* d_c,
+                          double* d_resp, double* d_q, double* d_ll, double* d_out, void* stream) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int32_t rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    return gmm_enqueue(ctx, mode, k, d_A, d_b, d_c, d_resp, d_q, d_ll, d_out, st);
+}
+
+int32_t psgd_gmm_responsibilities_device(psgd_ctx* ctx, int32_t k, const double* d_A, const double* d_b, const double* d_c,
+                                         double* d_resp, double* d_q, double* d_loglik, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_A || !d_b || !d_c || !d_resp || !d_loglik) return fail(PSGD_EINVAL, "d_A/d_b/d_c/d_resp/d_loglik are null");
+    const int32_t rc = gmm_args(k);
+    if (rc) return rc;
+    return gmm_device(ctx, kGmmResp, k, d_A, d_b, d_c, d_resp, d_q, d_loglik, nullptr, stream);
+}
+
+int32_t psgd_gmm_moments_device(psgd_ctx* ctx, int32_t k, const double* d_resp, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_resp || !d_out) return fail(PSGD_EINVAL, "d_resp/d_out are null");
+    const int32_t rc = gmm_args(k);
+    if (rc) return rc;
+    return gmm_device(ctx, kGmmMoments, k, nullptr, nullptr, nullptr, const_cast<double*>(d_resp), nullptr, nullptr, d_out,
+                      stream);
+}
+
+int32_t psgd_gmm_step_device(psgd_ctx* ctx, int32_t k, const double* d_A, const double* d_b, const double* d_c,
+                             double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_A || !d_b || !d_c || !d_out) return fail(PSGD_EINVAL, "d_A/d_b/d_c/d_out are null");
+    const int32_t rc = gmm_args(k);
+    if (rc) return rc;
+    return gmm_device(ctx, kGmmStep, k, d_A, d_b, d_c, nullptr, nullptr, nullptr, d_out, stream);
+}
+
+// The host-pointer forms: the model staged in, the results staged out through ctx->mixio:
+// [A k d d | b k d | c k | out k (d + 1)^2 + 2, or loglik 1, resp n k and q n k].
+static int32_t gmm_host(psgd_ctx* ctx, int32_t k, const double* A, const double* b, const double* c, double* resp,
+                        double* q, double* loglik, double* out) {
+    size_t n = 0, kdd = 0, kd = 0, len = 0, nk = 0;
+    double *d_A = nullptr, *d_res = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        const Part& first = ctx->parts.begin()->second;
+        const int32_t rows_rc = gmm_rows(first.layout, first.d);
+        if (rows_rc) return rows_rc;
+        const size_t d = (size_t)first.d;
+        for (auto& kv : ctx->parts) n += (size_t)kv.second.n_rows;
+        kd = (size_t)k * d;
+        kdd = kd * d;
+        nk = std::max<size_t>(n, 1) * (size_t)k;
+        len = out ? (size_t)k * (d + 1) * (d + 1) + 2 : 1 + 2 * nk;
+        DeviceGuard g(ctx->device);
+        // (the staging buffer is scratch too: a call on another stream may still use it)
+        const int32_t rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->mixio.ensure((kdd + kd + (size_t)k + len) * sizeof(double)));
+        d_A = ctx->mixio.as<double>();
+        d_res = d_A + kdd + kd + (size_t)k;
+        HIP_TRY(hipMemcpyAsync(d_A, A, kdd * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_A + kdd, b, kd * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_A + kdd + kd, c, (size_t)k * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        // the caller's arrays are pageable in general: the copies have left them when this returns
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    const double *d_b = d_A + kdd, *d_c = d_b + kd;
+    const int32_t rc = out ? gmm_device(ctx, kGmmStep, k, d_A, d_b, d_c, nullptr, nullptr, nullptr, d_res, ctx->stream)
+                           : gmm_device(ctx, kGmmResp, k, d_A, d_b, d_c, d_res + 1, q ? d_res + 1 + nk : nullptr, d_res,
+                                        nullptr, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    if (out) {
+        HIP_TRY(hipMemcpyAsync(out, d_res, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(loglik, d_res, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (n > 0) {
+            HIP_TRY(hipMemcpyAsync(resp, d_res + 1, n * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+            if (q) HIP_TRY(hipMemcpyAsync(q, d_res + 1 + nk, n * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_gmm_responsibilities(psgd_ctx* ctx, int32_t k, const double* A, const double* b, const double* c, double* resp,
+                                  double* q, double* loglik) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!A || !b || !c || !resp || !loglik) return fail(PSGD_EINVAL, "A/b/c/resp/loglik are null");
+    const int32_t rc = gmm_args(k);
+    if (rc) return rc;
+    return gmm_host(ctx, k, A, b, c, resp, q, loglik, nullptr);
+}
+
+int32_t psgd_gmm_step(psgd_ctx* ctx, int32_t k, const double* A, const double* b, const double* c, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!A || !b || !c || !out) return fail(PSGD_EINVAL, "A/b/c/out are null");
+    const int32_t rc = gmm_args(k);
+    if (rc) return rc;
+    return gmm_host(ctx, k, A, b, c, nullptr, nullptr, nullptr, out);
+}
+
+int32_t psgd_gmm_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t total_tiles, int64_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (layout != psgd::kDense && layout != psgd::kCsr) return fail(PSGD_EINVAL, "unknown layout " + std::to_string(layout));
+    if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
+    if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
+    if (total_tiles < 0) return fail(PSGD_EINVAL, "total_tiles must be >= 0");
+    int32_t rc = gmm_args(k);
+    if (rc) return rc;
+    rc = gmm_rows(layout, d);
+    if (rc) return rc;
+    const psgd::GmmGeom gm = psgd::gmm_geometry(storage == PSGD_F32 ? 1 : 0, d, k, total_tiles);
+    const int64_t resp_bytes = total_tiles * 16 * (int64_t)k * (int64_t)sizeof(double);
+    const int64_t v[PSGD_GMM_PLAN_LEN] = {gm.path, gm.cb,      gm.db,           gm.gr,
+                                          gm.gc,   gm.span,    gm.n_spans,      gm.n_items,
+                                          gm.scratch_bytes, gm.scratch_bytes + resp_bytes, gm.lds_bytes, gm.tile_rows,
+                                          gm.waves};
     std::memcpy(out, v, sizeof v);
     return PSGD_OK;
 }

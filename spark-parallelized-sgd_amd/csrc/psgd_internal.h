@@ -450,6 +450,43 @@ int launch_kmeans_step(const ChainDesc* descs, const KmPart* tab, int n_parts, i
 int launch_kmeans_update(int k, int d, const double* C, const double* step, double* c_new, double* moved,
                          hipStream_t st);
 
+// ---- One EM step of a Gaussian mixture (psgd_gmm.hip: psgd_gmm_responsibilities / _moments / _step) ----
+// The plan of a call: host code, no device (psgd_gmm_plan reports it). Dense rows only.
+enum GmmPath { kGmmDenseLds = 0, kGmmDenseL2 = 1 };
+constexpr int kGmmMaxK = 256;
+constexpr int kGmmMaxD = 256;
+struct GmmGeom {
+    int32_t d, k;
+    int32_t db, nb;          // column blocks of 16 a component (ceil(d / 16)), and of all k
+    int32_t path;            // GmmPath
+    int32_t cb;              // E-step: column blocks of a chunk (1, 2, 4)
+    int32_t dpad;            // d rounded up to whole steps of four 16-byte vectors
+    int32_t waves;           // E-step: waves a workgroup (8; 4 when eight waves' staging is past half a CU's LDS)
+    int32_t tile_rows;       // rows a tile: 16
+    int32_t a, nbz;          // moments: columns of z = [x, 1], their blocks of 16
+    int32_t gr, gc;          // moments: the rectangle of blocks a wave keeps
+    int32_t nrg, ncg;        // moments: rectangle rows and columns
+    int32_t n_groups;        // moments: rectangles that meet the upper triangle
+    int64_t span, n_spans;   // moments: tiles a span, spans
+    int64_t n_items;         // moments: spans x k x n_groups
+    int64_t lds_bytes;       // dynamic LDS of the E-step launch: the packed operands (LDS path), the waves' staging
+    int64_t op_doubles;      // the packed operands: dpad x 16 nb
+    int64_t scratch_bytes;   // scratch of a step but the responsibilities (bounded: n_items is capped)
+};
+GmmGeom gmm_geometry(int storage, int d, int k, int64_t n_tiles);
+// resp [rows][k] (row-major, local row order), q (nullable, the same shape) and loglik (one double) at the
+// packed-to-be A [k][d][d], b [k][d], c [k]; tab is the k-means passes' tile table; scratch is gm.scratch_bytes.
+int launch_gmm_estep(const ChainDesc* descs, const KmPart* tab, int n_parts, int64_t n_tiles, const GmmGeom& gm,
+                     int storage, const double* A, const double* b, const double* c, double* scratch, double* resp,
+                     double* q, double* loglik, int num_cus, hipStream_t st);
+// out[k (d + 1)^2] = S_j = sum_rows resp[row][j] z z^T, both triangles.
+int launch_gmm_moments(const ChainDesc* descs, const KmPart* tab, int n_parts, int64_t n_tiles, const GmmGeom& gm,
+                       int storage, const double* resp, double* scratch, double* out, hipStream_t st);
+// out[k (d + 1)^2 + 2] = {S, log-likelihood, n}: the E-step into resp [rows][k], then the moments.
+int launch_gmm_step(const ChainDesc* descs, const KmPart* tab, int n_parts, int64_t n_tiles, int64_t n_rows,
+                    const GmmGeom& gm, int storage, const double* A, const double* b, const double* c, double* scratch,
+                    double* resp, double* out, int num_cus, hipStream_t st);
+
 // w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
 // the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
 int64_t gd_update_blocks(int d);

@@ -858,6 +858,110 @@ class HipEngine(ShardedEngine):
         self.stream.synchronize()
         return new, moved
 
+    # Gaussian mixture (psgd_gmm_*_device; clustering.py) -------------------------------------------
+    def _gmm_operands(self, weights, gaussians):
+        """(k, [A | b | c] as one f64 device tensor) of a mixture of stat.MultivariateGaussian components
+        with weights `weights`: A_j = rootSigmaInv_j^T, b_j = rootSigmaInv_j mu_j, c_j = ln w_j + u_j
+        (self.stream is current). weights None: `gaussians` is the operands (A [k, d, d], b [k, d], c [k])
+        themselves."""
+        nf = self._data.num_features
+        if self._data.partitions and isinstance(self._data.partitions[0], (CsrPartition, DeviceCsrPartition)):
+            raise IllegalArgumentException(
+                "requirement failed: the Gaussian mixture needs dense rows (the partitions are CSR)")
+        if weights is None:
+            A, b, c = (np.ascontiguousarray(v, dtype=np.float64) for v in gaussians)
+            k = c.shape[0] if c.ndim == 1 else 0
+            if not 1 <= k <= N.GMM_MAX_K or A.shape != (k, nf, nf) or b.shape != (k, nf) or nf > N.GMM_MAX_D:
+                raise IllegalArgumentException(
+                    f"requirement failed: the operands must be A [k, {nf}, {nf}], b [k, {nf}], c [k] with 1 <= k <= "
+                    f"{N.GMM_MAX_K} and at most {N.GMM_MAX_D} features (got {A.shape}, {b.shape}, {c.shape})")
+            return k, self.torch.from_numpy(np.concatenate([A.reshape(-1), b.reshape(-1), c])).to(self.dev)
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        k = len(gaussians)
+        if w.shape != (k,) or not 1 <= k <= N.GMM_MAX_K or not np.all(w > 0.0):
+            raise IllegalArgumentException(
+                f"requirement failed: a mixture takes 1 <= k <= {N.GMM_MAX_K} components and one positive weight each "
+                f"(got {k} components, weights of shape {w.shape})")
+        if nf > N.GMM_MAX_D:
+            raise IllegalArgumentException(
+                f"requirement failed: the Gaussian mixture takes at most {N.GMM_MAX_D} features (got {nf})")
+        for g in gaussians:
+            if g.mu.shape[0] != nf:
+                raise IllegalArgumentException(
+                    f"requirement failed: vector sizes do not match: Expected {g.mu.shape[0]} but found {nf}")
+        A = np.stack([g.rootSigmaInv.T for g in gaussians])
+        b = np.stack([g.rootSigmaInv @ g.mu for g in gaussians])
+        c = np.log(w) + np.array([g.u for g in gaussians], dtype=np.float64)
+        host = np.concatenate([A.reshape(-1), b.reshape(-1), c])
+        return k, self.torch.from_numpy(host).to(self.dev)
+
+    def gmm_responsibilities(self, weights, gaussians, mahalanobis: bool = False):
+        """(resp, loglik, q) of every row of this rank's partitions under the mixture (`weights` [k],
+        `gaussians` k stat.MultivariateGaussian): resp a device tensor [local_rows(), k] of doubles in
+        partition and iterator order, loglik the sum of ln P over this rank's rows, q the Mahalanobis
+        forms in resp's shape (None unless `mahalanobis`); include/psgd.h has the semantics. The rows
+        are this rank's own, so the ranks exchange nothing here."""
+        torch = self.torch
+        n = self.local_rows()
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            k, abc = self._gmm_operands(weights, gaussians)
+            nf = self._data.num_features
+            resp = torch.zeros((max(n, 1), k), dtype=torch.float64, device=self.dev)
+            q = torch.zeros((max(n, 1), k), dtype=torch.float64, device=self.dev) if mahalanobis else None
+            ll = torch.zeros(1, dtype=torch.float64, device=self.dev)
+            if self.n_local > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    a_ptr = abc.data_ptr()
+                    self.ctx.gmm_responsibilities_device(k, a_ptr, a_ptr + 8 * k * nf * nf, a_ptr + 8 * (k * nf * nf + k * nf),
+                                                         resp.data_ptr(), 0 if q is None else q.data_ptr(), ll.data_ptr(),
+                                                         self.stream.cuda_stream)
+            loglik = float(ll.cpu().numpy()[0])   # (waits for the call: abc is a temporary of it)
+        caller.wait_stream(self.stream)
+        for t in (resp, q):
+            if t is not None:
+                t.record_stream(caller)
+        return resp[:n], loglik, None if q is None else q[:n]
+
+    def _resp_rows(self, resp):
+        """resp as a contiguous f64 device tensor [local_rows(), k] (self.stream is current)."""
+        if not self.torch.is_tensor(resp):
+            raise IllegalArgumentException("requirement failed: gmm_moments takes the responsibilities as a device tensor")
+        r = resp.detach().to(device=self.dev, dtype=self.torch.float64).contiguous()
+        n = self.local_rows()
+        if r.dim() != 2 or r.shape[0] != n or not 1 <= r.shape[1] <= N.GMM_MAX_K:
+            raise IllegalArgumentException(
+                f"requirement failed: the responsibilities must be [{n}, k] with 1 <= k <= {N.GMM_MAX_K} "
+                f"(got shape {tuple(r.shape)})")
+        if n == 0:   # (a valid pointer for a registry of empty partitions)
+            r = self.torch.zeros((1, r.shape[1]), dtype=self.torch.float64, device=self.dev)
+        return r
+
+    def gmm_moments(self, resp):
+        """S_j = sum_rows resp[row][j] z z^T, z = [x, 1], over every row of the data, on all ranks, as a
+        device tensor of k (d + 1)^2 doubles (psgd_gmm_moments_device). resp: a device tensor
+        [local_rows(), k], this rank's rows in partition and iterator order. The ranks all-gather their
+        moments and every rank adds them in rank order, as kmeans_step does."""
+        k, nf = int(resp.shape[1]) if self.torch.is_tensor(resp) and resp.dim() == 2 else 0, self._data.num_features
+        return self._batch_sum(max(k, 1) * (nf + 1) * (nf + 1), self._resp_rows, resp,
+                               lambda r_ptr, out: self.ctx.gmm_moments_device(k, r_ptr, out, self.stream.cuda_stream))
+
+    def gmm_step(self, weights, gaussians):
+        """{S[k][d + 1][d + 1], logLikelihood, n} of one EM step of the mixture over every row of the data,
+        on all ranks, as a device tensor of k (d + 1)^2 + 2 doubles (psgd_gmm_step_device). The ranks
+        all-gather their steps and every rank adds them in rank order, as kmeans_step does."""
+        self.stream.wait_stream(self.torch.cuda.current_stream(self.dev))
+        with self.torch.cuda.stream(self.stream):
+            k, abc = self._gmm_operands(weights, gaussians)   # (validated here)
+        nf = self._data.num_features
+        kdd, kd = k * nf * nf, k * nf
+        return self._batch_sum(k * (nf + 1) * (nf + 1) + 2, lambda t: t, abc,
+                               lambda a_ptr, out: self.ctx.gmm_step_device(k, a_ptr, a_ptr + 8 * kdd, a_ptr + 8 * (kdd + kd),
+                                                                           out, self.stream.cuda_stream))
+
     def registered_rows(self, positions) -> np.ndarray:
         """The rows at the global positions `positions` (partition order, then iterator order) as the
         engine registered them -- a column_transform applied the way the device applies it, CSR rows

@@ -314,3 +314,41 @@ def computeSVD(data: PartitionedData, k, computeU: bool = False, rCond: float = 
     s, V = gramian(data, engine=engine).svd(k, rCond)
     U = multiply(data, V / s[None, :], "f64", engine=engine) if computeU else None
     return U, s, V
+
+
+class MultivariateGaussian:
+    """MLlib 1.6.1 stat.distribution.MultivariateGaussian(mu, sigma) in numpy fp64, with the constants of
+    calculateCovarianceConstants: sigma = U diag(s) U^T by eigh, tol = EPS d max(s) with EPS = 2^-52,
+    rootSigmaInv = diag(s_pinv^(1/2)) U^T with zero rows where s <= tol (a singular sigma has a density on
+    its own support), u = -(d ln 2 pi + sum_{s > tol} ln s) / 2. logpdf(x) = u - ||rootSigmaInv (x - mu)||^2 / 2.
+    These are what clustering.GaussianMixture hands to the device (include/psgd.h, psgd_gmm_*)."""
+
+    EPS = 2.0 ** -52
+
+    def __init__(self, mu, sigma):
+        mu = np.ascontiguousarray(mu, dtype=np.float64)
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        if mu.ndim != 1 or mu.shape[0] < 1:
+            raise IllegalArgumentException(f"requirement failed: mu must be a vector (got shape {mu.shape})")
+        d = mu.shape[0]
+        if sigma.shape != (d, d):
+            raise IllegalArgumentException(
+                f"requirement failed: Mean vector length must match covariance matrix size (got {d} and {sigma.shape})")
+        s, U = np.linalg.eigh(0.5 * (sigma + sigma.T))
+        tol = self.EPS * d * float(np.max(s))
+        keep = s > tol
+        if not np.any(keep):
+            raise IllegalArgumentException("requirement failed: covariance matrix has no non-zero singular values")
+        root = np.where(keep, 1.0 / np.sqrt(np.where(keep, s, 1.0)), 0.0)
+        self.mu, self.sigma = mu, sigma
+        self.rootSigmaInv = np.ascontiguousarray(root[:, None] * U.T)
+        self.u = -0.5 * (d * np.log(2.0 * np.pi) + float(np.sum(np.log(s[keep]))))
+
+    def logpdf(self, x):
+        """ln pdf of a vector [d] or of each row of [n, d]."""
+        delta = np.asarray(x, dtype=np.float64) - self.mu
+        v = delta @ self.rootSigmaInv.T
+        return self.u - 0.5 * np.sum(v * v, axis=-1)
+
+    def pdf(self, x):
+        return np.exp(self.logpdf(x))
