@@ -387,6 +387,35 @@ int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes,
 int32_t psgd_gradient_multinomial_plan(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
                                        int64_t max_nnz, int32_t* out);
 
+/* The three calls above with the method as an argument. PSGD_MN_METHOD_AUTO is the calls above: their
+ * plan, kernels and bits. PSGD_MN_METHOD_MFMA runs the fp64 matrix-core path (psgd_grad_mn_mfma.hip):
+ * the same output definition, per-row math, batch, ordering and scratch; no floating-point atomics, the
+ * same bits from call to call (PSGD_GRAD_MN_RANGE changes none of them); it agrees with the other
+ * dense paths to rounding, not bit for bit. It serves dense rows, num_classes <= 65 and d <= 4,096:
+ * anything else is PSGD_EUNSUPPORTED from the plan and from the call (more classes would need the
+ * margins parked across class chunks and the rows read twice). An unknown method is PSGD_EINVAL.
+ * For this path the plan's out[] is
+ *   [0] 4;
+ *   [1] class blocks of 16, ceil((K - 1) / 16);
+ *   [2] 1 when the multiplier pass reads the packed W from LDS (dpad * 16 * [1] * 8 bytes <= 160 KiB),
+ *       0 when it reads it through L2;
+ *   [3] 0 (the softmax runs across the 16 lanes of a DPP row);
+ *   [4] rows of a tile;
+ *   [5] dpad, the features of the packed W (d rounded up to 4 row vectors);
+ *   [6] class blocks and [7] feature blocks of the accumulation pass's rectangle (one wave's
+ *       accumulators); [8] rectangles across the features; [9] rectangles across the classes (1);
+ *   [10] consecutive tiles a gradient record covers; [11] tiles of a row range. */
+#define PSGD_MN_METHOD_AUTO 0
+#define PSGD_MN_METHOD_MFMA 1
+int32_t psgd_gradient_sum_multinomial_method(psgd_ctx* ctx, int32_t num_classes, const double* w,
+                                             double mini_batch_fraction, int32_t iteration, int32_t method,
+                                             double* out);
+int32_t psgd_gradient_sum_multinomial_method_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w,
+                                                    double mini_batch_fraction, int32_t iteration, int32_t method,
+                                                    double* d_out, void* stream);
+int32_t psgd_gradient_multinomial_plan_method(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
+                                              int64_t max_nnz, int32_t method, int32_t* out);
+
 /* The augmented Gramian over every registered row -- the second-moment pass behind MLlib 1.6.1's
  * RowMatrix.computeGramianMatrix / computeCovariance, Statistics.corr and the normal equations of
  * least squares. With z_i = [x_i0 .. x_i,d-1, y_i, 1] (a = d + 2 columns; the stored values widened to

@@ -33,6 +33,8 @@ EXPORTED = (
     "psgd_column_stats", "psgd_column_stats_device", "psgd_transform_columns", "psgd_transform_columns_device",
     "psgd_gradient_sum", "psgd_gradient_sum_device", "psgd_gd_update", "psgd_gd_update_device",
     "psgd_gradient_sum_multinomial", "psgd_gradient_sum_multinomial_device", "psgd_gradient_multinomial_plan",
+    "psgd_gradient_sum_multinomial_method", "psgd_gradient_sum_multinomial_method_device",
+    "psgd_gradient_multinomial_plan_method",
     "psgd_gramian", "psgd_gramian_device", "psgd_gramian_plan",
     "psgd_gramian_weighted", "psgd_gramian_weighted_device", "psgd_local_rows",
     "psgd_row_curvature", "psgd_row_curvature_device",
@@ -151,6 +153,11 @@ def lib():
             "psgd_gradient_sum_multinomial": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp], C.c_int32),
             "psgd_gradient_sum_multinomial_device": ([vp, C.c_int32, vp, C.c_double, C.c_int32, vp, vp], C.c_int32),
             "psgd_gradient_multinomial_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
+            "psgd_gradient_sum_multinomial_method": ([vp, C.c_int32, vp, C.c_double, C.c_int32, C.c_int32, vp], C.c_int32),
+            "psgd_gradient_sum_multinomial_method_device": ([vp, C.c_int32, vp, C.c_double, C.c_int32, C.c_int32, vp, vp],
+                                                            C.c_int32),
+            "psgd_gradient_multinomial_plan_method": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32,
+                                                       vp], C.c_int32),
             "psgd_gramian": ([vp, vp], C.c_int32),
             "psgd_gramian_device": ([vp, vp, vp], C.c_int32),
             "psgd_gramian_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
@@ -256,18 +263,32 @@ def multiclass_switches() -> dict:
     return {"lds_weights": int(out[0]), "lane_classes": int(out[1]), "confusion_lds_cells": int(out[2])}
 
 
-MN_GRAD_PATHS = ("fused", "general", "csr_lds", "csr_global")   # psgd_gradient_multinomial_plan's out[0]
+MN_GRAD_PATHS = ("fused", "general", "csr_lds", "csr_global", "mfma")   # psgd_gradient_multinomial_plan's out[0]
+MN_METHODS = {"auto": 0, "mfma": 1}   # PSGD_MN_METHOD_*
 
 
-def gradient_multinomial_plan(layout: str, storage: str, d: int, num_classes: int, max_nnz: int = 0) -> dict:
-    """Which kernels psgd_gradient_sum_multinomial runs for rows of `layout` ("dense" / "csr") stored
-    as `storage` ("f32" / "f64"), with the environment switches as they are now
-    (psgd_gradient_multinomial_plan: host code, no device)."""
+def mn_method(method: str) -> int:
+    """"auto" (the plan's own choice of the fused, general and CSR kernels) or "mfma" (the fp64
+    matrix-core path: dense rows, numClasses <= 65, d <= 4,096) -> PSGD_MN_METHOD_*."""
+    if method not in MN_METHODS:
+        raise IllegalArgumentException(f"unknown multinomial gradient method {method!r}: 'auto' or 'mfma'")
+    return MN_METHODS[method]
+
+
+def gradient_multinomial_plan(layout: str, storage: str, d: int, num_classes: int, max_nnz: int = 0,
+                              method: str = "auto") -> dict:
+    """Which kernels psgd_gradient_sum_multinomial_method runs for rows of `layout` ("dense" / "csr")
+    stored as `storage` ("f32" / "f64"), with the environment switches as they are now
+    (psgd_gradient_multinomial_plan_method: host code, no device). The "mfma" plan has keys of its own:
+    the class blocks of 16, the packed W's features, the accumulation pass's rectangle."""
     out = (C.c_int32 * 12)()
-    check(lib().psgd_gradient_multinomial_plan({"dense": 0, "csr": 1}[layout], {"f64": 0, "f32": 1}[storage],
-                                               int(d), int(num_classes), int(max_nnz), out))
+    check(lib().psgd_gradient_multinomial_plan_method({"dense": 0, "csr": 1}[layout], {"f64": 0, "f32": 1}[storage],
+                                                      int(d), int(num_classes), int(max_nnz), mn_method(method), out))
     keys = ("path", "group", "weights_in_lds", "wide_softmax", "tile_rows", "nvl", "class_accumulators",
             "acc_group", "col_chunks", "class_chunks", "span", "range")
+    if MN_GRAD_PATHS[out[0]] == "mfma":
+        keys = ("path", "class_blocks", "weights_in_lds", "wide_softmax", "tile_rows", "dpad", "rect_class_blocks",
+                "rect_feature_blocks", "col_chunks", "class_chunks", "span", "range")
     plan = {k: int(v) for k, v in zip(keys, out)}
     plan["path"] = MN_GRAD_PATHS[plan["path"]]
     return plan
@@ -772,20 +793,23 @@ class Context:
         check(self._L.psgd_gradient_sum_device(self.handle, int(gradient), w_ptr, float(fraction), int(iteration),
                                                out_ptr, stream))
 
-    def gradient_sum_multinomial(self, num_classes: int, w, fraction: float = 1.0, iteration: int = 0):
-        """Host-pointer form (psgd_gradient_sum_multinomial): the (K - 1) d + 2 doubles {gradientSum,
-        lossSum, count} of the (K - 1) d host weights w over the batch."""
+    def gradient_sum_multinomial(self, num_classes: int, w, fraction: float = 1.0, iteration: int = 0,
+                                 method: str = "auto"):
+        """Host-pointer form (psgd_gradient_sum_multinomial_method): the (K - 1) d + 2 doubles
+        {gradientSum, lossSum, count} of the (K - 1) d host weights w over the batch; method as mn_method."""
         import numpy as np
         w = np.ascontiguousarray(w, dtype=np.float64)
         out = np.zeros(w.shape[0] + 2, dtype=np.float64)
-        check(self._L.psgd_gradient_sum_multinomial(self.handle, int(num_classes), w.ctypes.data, float(fraction),
-                                                    int(iteration), out.ctypes.data))
+        check(self._L.psgd_gradient_sum_multinomial_method(self.handle, int(num_classes), w.ctypes.data,
+                                                           float(fraction), int(iteration), mn_method(method),
+                                                           out.ctypes.data))
         return out
 
-    def gradient_sum_multinomial_device(self, num_classes: int, w_ptr, fraction, iteration, out_ptr, stream=None):
-        """psgd_gradient_sum_multinomial_device: enqueued on `stream`; out[(K - 1) d + 2] on the device."""
-        check(self._L.psgd_gradient_sum_multinomial_device(self.handle, int(num_classes), w_ptr, float(fraction),
-                                                           int(iteration), out_ptr, stream))
+    def gradient_sum_multinomial_device(self, num_classes: int, w_ptr, fraction, iteration, out_ptr, stream=None,
+                                        method: str = "auto"):
+        """psgd_gradient_sum_multinomial_method_device: enqueued on `stream`; out[(K - 1) d + 2] on the device."""
+        check(self._L.psgd_gradient_sum_multinomial_method_device(self.handle, int(num_classes), w_ptr, float(fraction),
+                                                                  int(iteration), mn_method(method), out_ptr, stream))
 
     def gd_update(self, updater: int, w, gsum, step: float, iteration: int, reg: float):
         """Host-pointer form (psgd_gd_update): (w', regVal) of one GradientDescent update."""

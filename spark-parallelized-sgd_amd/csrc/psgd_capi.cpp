@@ -2444,11 +2444,33 @@ static int32_t gradient_mn_args(int32_t num_classes, double fraction) {
     return gradient_args(PSGD_GRADIENT_LOGISTIC, fraction);
 }
 
-int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w,
-                                             double mini_batch_fraction, int32_t iteration, double* d_out,
-                                             void* stream) {
+static int32_t gradient_mn_method(int32_t method) {
+    if (method != PSGD_MN_METHOD_AUTO && method != PSGD_MN_METHOD_MFMA)
+        return fail(PSGD_EINVAL, "unknown multinomial gradient method " + std::to_string(method));
+    return PSGD_OK;
+}
+
+// What PSGD_MN_METHOD_MFMA does not serve, by the limit it misses.
+static int32_t gradient_mn_mfma_serves(int layout, int32_t d, int32_t num_classes) {
+    if (psgd::grad_mn_mfma_serves(layout, d, num_classes)) return PSGD_OK;
+    std::string why = layout != psgd::kDense ? "CSR rows"
+                      : num_classes - 1 > psgd::kMnMfmaClasses
+                          ? "numClasses = " + std::to_string(num_classes) + " (at most " +
+                                std::to_string(psgd::kMnMfmaClasses + 1) + " classes)"
+                          : "d = " + std::to_string(d) + " (at most " + std::to_string(psgd::kMnMfmaFeatures) +
+                                " features)";
+    return fail(PSGD_EUNSUPPORTED, "the MFMA multinomial gradient serves dense rows, numClasses <= " +
+                                       std::to_string(psgd::kMnMfmaClasses + 1) + " and d <= " +
+                                       std::to_string(psgd::kMnMfmaFeatures) + ": not " + why);
+}
+
+int32_t psgd_gradient_sum_multinomial_method_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w,
+                                                    double mini_batch_fraction, int32_t iteration, int32_t method,
+                                                    double* d_out, void* stream) {
     if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
     int32_t rc = gradient_mn_args(num_classes, mini_batch_fraction);
+    if (rc) return rc;
+    rc = gradient_mn_method(method);
     if (rc) return rc;
     if (!d_w || !d_out) return fail(PSGD_EINVAL, "d_w/d_out are null");
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -2463,6 +2485,10 @@ int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes,
     const int P = (int)ctx->parts.size();
     const int storage = first.dtype == PSGD_F32 ? 1 : 0;
     const size_t len = (size_t)(num_classes - 1) * (size_t)d + 2;
+    if (method == PSGD_MN_METHOD_MFMA) {
+        rc = gradient_mn_mfma_serves(first.layout, d, num_classes);
+        if (rc) return rc;
+    }
     if (mini_batch_fraction <= 0.0) {   // RDD.sample(false, 0, .): every partition's batch is empty
         HIP_TRY(hipMemsetAsync(d_out, 0, len * sizeof(double), st));
         return PSGD_OK;
@@ -2473,7 +2499,7 @@ int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes,
     rc = gradient_batch(ctx, mini_batch_fraction, iteration, st, &descs);
     if (rc) return rc;
     const int64_t n_tiles = ctx->stat_tile0.back();
-    const psgd::MnGradGeom gm = psgd::grad_mn_geometry(first.layout, storage, d, num_classes, max_nnz);
+    const psgd::MnGradGeom gm = psgd::grad_mn_geometry(first.layout, storage, d, num_classes, max_nnz, method);
     HIP_TRY(ctx->grec.ensure((psgd::grad_mn_scratch(gm, n_tiles) + 1) * sizeof(double)));
     const int e = psgd::launch_gradient_mn(descs, ctx->stile0.as<int64_t>(), P, n_tiles, gm, storage, d_w,
                                            ctx->grec.as<double>(), d_out, ctx->num_cus, st);
@@ -2481,10 +2507,20 @@ int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes,
     return PSGD_OK;
 }
 
-int32_t psgd_gradient_sum_multinomial(psgd_ctx* ctx, int32_t num_classes, const double* w,
-                                      double mini_batch_fraction, int32_t iteration, double* out) {
+int32_t psgd_gradient_sum_multinomial_device(psgd_ctx* ctx, int32_t num_classes, const double* d_w,
+                                             double mini_batch_fraction, int32_t iteration, double* d_out,
+                                             void* stream) {
+    return psgd_gradient_sum_multinomial_method_device(ctx, num_classes, d_w, mini_batch_fraction, iteration,
+                                                       PSGD_MN_METHOD_AUTO, d_out, stream);
+}
+
+int32_t psgd_gradient_sum_multinomial_method(psgd_ctx* ctx, int32_t num_classes, const double* w,
+                                             double mini_batch_fraction, int32_t iteration, int32_t method,
+                                             double* out) {
     if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
     int32_t rc = gradient_mn_args(num_classes, mini_batch_fraction);
+    if (rc) return rc;
+    rc = gradient_mn_method(method);
     if (rc) return rc;
     if (!w || !out) return fail(PSGD_EINVAL, "w/out are null");
     size_t n = 0;
@@ -2504,7 +2540,8 @@ int32_t psgd_gradient_sum_multinomial(psgd_ctx* ctx, int32_t num_classes, const 
         // the caller's array is pageable in general: the copy has left it when this returns
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    rc = psgd_gradient_sum_multinomial_device(ctx, num_classes, d_w, mini_batch_fraction, iteration, d_out, ctx->stream);
+    rc = psgd_gradient_sum_multinomial_method_device(ctx, num_classes, d_w, mini_batch_fraction, iteration, method,
+                                                     d_out, ctx->stream);
     if (rc) return rc;
     DeviceGuard g(ctx->device);
     HIP_TRY(hipMemcpyAsync(out, d_out, (n + 2) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -2512,21 +2549,44 @@ int32_t psgd_gradient_sum_multinomial(psgd_ctx* ctx, int32_t num_classes, const 
     return PSGD_OK;
 }
 
-int32_t psgd_gradient_multinomial_plan(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
-                                       int64_t max_nnz, int32_t* out) {
+int32_t psgd_gradient_sum_multinomial(psgd_ctx* ctx, int32_t num_classes, const double* w,
+                                      double mini_batch_fraction, int32_t iteration, double* out) {
+    return psgd_gradient_sum_multinomial_method(ctx, num_classes, w, mini_batch_fraction, iteration,
+                                                PSGD_MN_METHOD_AUTO, out);
+}
+
+int32_t psgd_gradient_multinomial_plan_method(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
+                                              int64_t max_nnz, int32_t method, int32_t* out) {
     if (!out) return fail(PSGD_EINVAL, "out is null");
     if (layout != psgd::kDense && layout != psgd::kCsr) return fail(PSGD_EINVAL, "unknown layout " + std::to_string(layout));
     if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
     if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
     if (max_nnz < 0) return fail(PSGD_EINVAL, "max_nnz must be >= 0");
-    const int32_t rc = gradient_mn_args(num_classes, 1.0);
+    int32_t rc = gradient_mn_args(num_classes, 1.0);
     if (rc) return rc;
-    const psgd::MnGradGeom gm = psgd::grad_mn_geometry(layout,
-                                                       storage == PSGD_F32 ? 1 : 0, d, num_classes, max_nnz);
+    rc = gradient_mn_method(method);
+    if (rc) return rc;
+    if (method == PSGD_MN_METHOD_MFMA) {
+        rc = gradient_mn_mfma_serves(layout, d, num_classes);
+        if (rc) return rc;
+    }
+    const psgd::MnGradGeom gm = psgd::grad_mn_geometry(layout, storage == PSGD_F32 ? 1 : 0, d, num_classes, max_nnz,
+                                                       method);
+    if (gm.path == psgd::kMnGradMfma) {
+        const int32_t v[PSGD_MN_PLAN_LEN] = {gm.path, gm.nb, gm.wlds,        gm.wide,          gm.tile_rows, gm.dpad,
+                                             gm.gr,   gm.gc, gm.n_colchunks, gm.n_classchunks, gm.span,      gm.range};
+        std::memcpy(out, v, sizeof v);
+        return PSGD_OK;
+    }
     const int32_t v[PSGD_MN_PLAN_LEN] = {gm.path, gm.group,   gm.wlds,       gm.wide,         gm.tile_rows, gm.nvl,
                                          gm.cp,   gm.agroup,  gm.n_colchunks, gm.n_classchunks, gm.span,      gm.range};
     std::memcpy(out, v, sizeof v);
     return PSGD_OK;
+}
+
+int32_t psgd_gradient_multinomial_plan(int32_t layout, int32_t storage, int32_t d, int32_t num_classes,
+                                       int64_t max_nnz, int32_t* out) {
+    return psgd_gradient_multinomial_plan_method(layout, storage, d, num_classes, max_nnz, PSGD_MN_METHOD_AUTO, out);
 }
 
 // ---- The augmented Gramian (kernels in psgd_gram.hip) ----

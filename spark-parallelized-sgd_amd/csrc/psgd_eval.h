@@ -72,6 +72,12 @@ __device__ __forceinline__ double mn_loss(double sum, double marginY, double M, 
     return loss;
 }
 
+// The multinomial gradient's indicator of class c + 1 (class 0 is the pivot; a label that is no class
+// matches nothing).
+__device__ __forceinline__ double mn_indicator(double y, int c) {
+    return (y != 0.0 && y == (double)(c + 1)) ? 1.0 : 0.0;
+}
+
 // The margin buffer's shape for a partition whose wave pass could take `rpw` groups of `rows` rows:
 // pitch of a row, groups a pass uses (rp <= rpw) and rows the buffer holds before it is scored (nb, a
 // multiple of rp * rows).

@@ -37,6 +37,9 @@
 //   range tile_rows C1 <= max(kGmMultDoubles = 2^25, tile_rows C1) (multipliers: 256 MiB, or one tile's).
 //   Neither span nor range changes a bit of the result's order within a span; PSGD_GRAD_MN_RANGE=n
 //   (tests) shortens the ranges to at most n tiles.
+//   MFMA (method kMnMfma only, never chosen here: psgd_grad_mn_mfma.hip has the kernels): the general
+//   path's ranges, records and merge with span = 1, 2 or 4 tiles, and the packed W (dpad x 16 nb
+//   doubles) behind the multipliers in the scratch.
 //
 // CSR rows, gradientSum NOT bitwise reproducible (lossSum and count are): one pass as grad_csr. A
 // wave gathers the margins of the rows its buffer holds in score_csr_mn's entry loop, turns them into
@@ -62,10 +65,6 @@ constexpr int kGmChunkVecs = 2;            // accumulation pass: row vectors a l
 constexpr int kGmChunkClasses = 8;         // accumulation pass: classes a lane owns
 constexpr int64_t kGmMultDoubles = 1ll << 25;   // multipliers a range holds (256 MiB)
 constexpr int kGmCsrWaves = 8;
-
-__device__ __forceinline__ double mn_indicator(double y, int c) {
-    return (y != 0.0 && y == (double)(c + 1)) ? 1.0 : 0.0;
-}
 
 // Row-per-lane: rows row0 .. row0 + n (n <= 64) of the batch at marg[i * pitch + c]; lane i replaces
 // row i's margins by its multipliers, classes in order (the reference's order), and adds its loss.
@@ -787,23 +786,24 @@ int64_t merged_spans(int64_t T) {
     return (T + s - 1) / s;
 }
 
-// The scratch: [rec: n x C1 d | rec2 | lrec: T x 2 | lrec2 | mult].
+// The scratch: [rec: n x C1 d | rec2 | lrec: T x 2 | lrec2 | mult | the MFMA path's packed W].
 struct MnScratch {
     int64_t n_rec;
-    size_t rec2, lrec, lrec2, mult, total;
+    size_t rec2, lrec, lrec2, mult, pack, total;
 };
 MnScratch mn_scratch(const MnGradGeom& gm, int64_t n_tiles) {
     MnScratch s{};
     const int64_t T = std::max<int64_t>(n_tiles, 1);
     const size_t Wg = (size_t)gm.C1 * (size_t)gm.d;
-    s.n_rec = gm.path == kMnGradFused ? T : gm.path == kMnGradGeneral ? (T + gm.span - 1) / gm.span : 0;
+    const bool ranged = gm.path == kMnGradGeneral || gm.path == kMnGradMfma;
+    s.n_rec = gm.path == kMnGradFused ? T : ranged ? (T + gm.span - 1) / gm.span : 0;
     s.rec2 = (size_t)s.n_rec * Wg;
     s.lrec = s.rec2 + (s.n_rec ? (size_t)merged_spans(s.n_rec) * Wg : 0);
     s.lrec2 = s.lrec + 2 * (size_t)T;
     s.mult = s.lrec2 + 2 * (size_t)merged_spans(T);
-    s.total = s.mult + (gm.path == kMnGradGeneral
-                            ? (size_t)std::min<int64_t>(gm.range, T) * (size_t)gm.tile_rows * (size_t)gm.C1
-                            : 0);
+    s.pack = s.mult + (ranged ? (size_t)std::min<int64_t>(gm.range, T) * (size_t)gm.tile_rows * (size_t)gm.C1 : 0);
+    if (gm.path == kMnGradMfma) s.pack = (s.pack + 1) & ~(size_t)1;   // (the packed W is read as 16-byte pairs)
+    s.total = s.pack + (gm.path == kMnGradMfma ? grad_mn_mfma_pack_doubles(gm) : 0);
     return s;
 }
 
@@ -818,15 +818,38 @@ int pow2_at_least(int64_t n) {
     return p;
 }
 
+// The tiles of a range: the most (a power of two) whose multipliers fit kGmMultDoubles.
+// PSGD_GRAD_MN_RANGE=n (tests): at most n tiles a range, so that a small batch takes several.
+int32_t mn_range(const MnGradGeom& gm) {
+    int64_t range = 1;
+    while (2 * range * gm.tile_rows * gm.C1 <= kGmMultDoubles && range < (1 << 30)) range *= 2;
+    if (const char* e = getenv("PSGD_GRAD_MN_RANGE")) {
+        const long cap = atol(e);
+        while (cap >= 1 && range > cap) range /= 2;
+    }
+    return (int32_t)range;
+}
+
 }  // namespace
+
+bool grad_mn_mfma_serves(int layout, int d, int num_classes) {
+    return layout == kDense && num_classes - 1 <= kMnMfmaClasses && d <= kMnMfmaFeatures;
+}
 
 // PSGD_GRAD_MN_TWO_PASS=1 (tests, A/B): a dense shape that would run fused takes the general path.
 // Read at every call, like PSGD_GRAD_CSR_GLOBAL.
-MnGradGeom grad_mn_geometry(int layout, int storage, int d, int num_classes, int64_t max_nnz) {
+MnGradGeom grad_mn_geometry(int layout, int storage, int d, int num_classes, int64_t max_nnz, int method) {
     MnGradGeom gm{};
     gm.d = d;
     gm.C1 = num_classes - 1;
     gm.tile_rows = stats_geometry(layout, d, storage).tile_rows;
+    if (method == kMnMfma) {
+        gm.path = kMnGradMfma;
+        gm.nvec = (d + (storage == 1 ? 4 : 2) - 1) / (storage == 1 ? 4 : 2);
+        grad_mn_mfma_geometry(gm, storage);
+        gm.range = mn_range(gm);
+        return gm;
+    }
     gm.wide = gm.C1 > kMnLaneClasses ? 1 : 0;
     gm.span = 1;
     if (layout == kCsr) {
@@ -864,14 +887,7 @@ MnGradGeom grad_mn_geometry(int layout, int storage, int d, int num_classes, int
     const int per_item = (64 / gm.agroup) * kGmChunkClasses;
     gm.n_classchunks = (gm.C1 + per_item - 1) / per_item;
     gm.span = pow2_at_least((gm.C1 + 15) / 16);
-    int64_t range = 1;
-    while (2 * range * gm.tile_rows * gm.C1 <= kGmMultDoubles && range < (1 << 30)) range *= 2;
-    // PSGD_GRAD_MN_RANGE=n (tests): at most n tiles a range, so that a small batch takes several
-    if (const char* e = getenv("PSGD_GRAD_MN_RANGE")) {
-        const long cap = atol(e);
-        while (cap >= 1 && range > cap) range /= 2;
-    }
-    gm.range = (int32_t)range;
+    gm.range = mn_range(gm);
     return gm;
 }
 
@@ -893,6 +909,9 @@ int launch_gradient_mn(const ChainDesc* descs, const int64_t* tile0, int n_parts
     if (csr)
         e = storage == 1 ? launch_csr_s<float>(gm, num_cus, st, descs, tile0, n_parts, n_tiles, w, out, lrec)
                          : launch_csr_s<double>(gm, num_cus, st, descs, tile0, n_parts, n_tiles, w, out, lrec);
+    else if (gm.path == kMnGradMfma)
+        e = launch_gradient_mn_mfma(descs, tile0, n_parts, n_tiles, gm, storage, w, rec, lrec, scratch + s.mult,
+                                    scratch + s.pack, num_cus, st);
     else if (gm.path == kMnGradFused)
         e = storage == 1 ? launch_fused_s<float>(gm, num_cus, st, descs, tile0, n_parts, n_tiles, w, rec, lrec)
                          : launch_fused_s<double>(gm, num_cus, st, descs, tile0, n_parts, n_tiles, w, rec, lrec);

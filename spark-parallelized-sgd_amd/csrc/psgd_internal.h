@@ -314,7 +314,13 @@ int grad_merge_records(const double* rec, int64_t T, int64_t W, double* rec2, do
 // ---- The batch gradient of the multinomial LogisticGradient (psgd_grad_mn.hip) ----
 // Which kernels a call runs and their geometry: host code, no device (psgd_gradient_multinomial_plan
 // reports it). The tiling is the statistics passes'.
-enum MnGradPath { kMnGradFused = 0, kMnGradGeneral = 1, kMnGradCsrLds = 2, kMnGradCsrGlobal = 3 };
+enum MnGradPath { kMnGradFused = 0, kMnGradGeneral = 1, kMnGradCsrLds = 2, kMnGradCsrGlobal = 3, kMnGradMfma = 4 };
+// How the path is chosen: kMnAuto is grad_mn_geometry's own rule (fused / general / CSR); kMnMfma asks
+// for the fp64 matrix-core path (psgd_grad_mn_mfma.hip), which serves dense rows with K - 1 <=
+// kMnMfmaClasses and d <= kMnMfmaFeatures and nothing else.
+enum MnGradMethod { kMnAuto = 0, kMnMfma = 1 };
+constexpr int kMnMfmaClasses = 64;
+constexpr int kMnMfmaFeatures = 4096;
 struct MnGradGeom {
     int32_t d, C1;        // features, K - 1
     int32_t tile_rows;
@@ -327,10 +333,26 @@ struct MnGradGeom {
     int32_t agroup;       // general, accumulation pass: lanes across a column chunk (64 / agroup class chunks a wave)
     int32_t n_colchunks, n_classchunks;
     int32_t span;         // general: consecutive tiles one gradient record covers (1: a record a tile)
-    int32_t range;        // general: tiles whose multipliers the scratch holds at a time
+    int32_t range;        // general, MFMA: tiles whose multipliers the scratch holds at a time
+    // MFMA (path kMnGradMfma; wlds, span and range above apply too)
+    int32_t nb;           // class blocks of 16: ceil((K - 1) / 16) <= 4
+    int32_t dpad;         // features of the packed W: d rounded up to 4 row vectors
+    int32_t gr, gc;       // accumulation pass: a wave's rectangle of class blocks x feature blocks
+    int32_t ncg;          // accumulation pass: rectangles across the features
 };
-// Reads PSGD_GRAD_MN_TWO_PASS and PSGD_GRAD_CSR_GLOBAL. num_classes in [3, kMultinomialMaxBlocks + 1].
-MnGradGeom grad_mn_geometry(int layout, int storage, int d, int num_classes, int64_t max_nnz);
+// Reads PSGD_GRAD_MN_TWO_PASS, PSGD_GRAD_CSR_GLOBAL and PSGD_GRAD_MN_RANGE. num_classes in [3,
+// kMultinomialMaxBlocks + 1]; method kMnMfma only for a shape grad_mn_mfma_serves.
+MnGradGeom grad_mn_geometry(int layout, int storage, int d, int num_classes, int64_t max_nnz, int method = kMnAuto);
+bool grad_mn_mfma_serves(int layout, int d, int num_classes);
+// The MFMA path's own part of the geometry (psgd_grad_mn_mfma.hip); gm.d, C1 and tile_rows are set.
+void grad_mn_mfma_geometry(MnGradGeom& gm, int storage);
+// Doubles of the packed W.
+size_t grad_mn_mfma_pack_doubles(const MnGradGeom& gm);
+// The MFMA path's passes over all ranges: rec [ceil(n_tiles / span)][C1 d], lrec [n_tiles][2], mult
+// [min(range, n_tiles) tile_rows C1], wp [grad_mn_mfma_pack_doubles].
+int launch_gradient_mn_mfma(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles,
+                            const MnGradGeom& gm, int storage, const double* w, double* rec, double* lrec,
+                            double* mult, double* wp, int num_cus, hipStream_t st);
 // Doubles of scratch a call over n_tiles tiles needs (the bound is in psgd_grad_mn.hip's header).
 size_t grad_mn_scratch(const MnGradGeom& gm, int64_t n_tiles);
 // out[(K - 1) d + 2] = {gradientSum, lossSum, count} over the batch rows of descs[0 .. n_parts) at

@@ -60,6 +60,12 @@ def _check_multinomial_kinds(gradient: Gradient, updater: SGDUpdater = None) -> 
     return check_num_classes(num_classes(gradient))
 
 
+def _method_kw(method: str) -> dict:
+    """The engine call's method argument: validated, and left out for "auto" (the engine's default)."""
+    N.mn_method(method)
+    return {} if method == "auto" else {"method": method}
+
+
 def _check_fraction(miniBatchFraction: float) -> None:
     if not (0.0 <= miniBatchFraction <= 1.0):
         raise IllegalArgumentException(
@@ -86,12 +92,13 @@ def gradient_sum(data: PartitionedData, gradient: Gradient, weights, miniBatchFr
 
 
 def gradient_sum_multinomial(data: PartitionedData, gradient: Gradient, weights, miniBatchFraction: float = 1.0,
-                             iteration: int = 0, *, engine=None) -> GradientSum:
+                             iteration: int = 0, *, engine=None, method: str = "auto") -> GradientSum:
     """gradient_sum() for LogisticGradient(numClasses = K > 2): `weights` are (K - 1) * num_features
     doubles in K - 1 class blocks (class 0 the pivot), and so is the gradient -- the slope of
-    evaluate_multinomial()'s lossSum (psgd_gradient_sum_multinomial). A binary gradient raises
-    IllegalArgumentException."""
+    evaluate_multinomial()'s lossSum (psgd_gradient_sum_multinomial_method). A binary gradient raises
+    IllegalArgumentException. method: "auto" or "mfma" (HipEngine.gradient_sum_multinomial)."""
     K = _check_multinomial_kinds(gradient)
+    N.mn_method(method)
     _check_fraction(miniBatchFraction)
     if data.num_partitions == 0:
         return GradientSum(np.zeros(0), 0.0, 0)
@@ -99,7 +106,7 @@ def gradient_sum_multinomial(data: PartitionedData, gradient: Gradient, weights,
     if engine is None:
         rank, world, _ = _dist()
         engine = HipEngine(data, rank, world, weight_dim=(K - 1) * data.num_features)
-    h = engine.to_host(engine.gradient_sum_multinomial(K, weights, miniBatchFraction, iteration))
+    h = engine.to_host(engine.gradient_sum_multinomial(K, weights, miniBatchFraction, iteration, **_method_kw(method)))
     return GradientSum(h[:-2].copy(), float(h[-2]), int(h[-1]))
 
 
@@ -114,12 +121,22 @@ class GradientDescent(ParallelizedSGD):
             raise N.UnsupportedOperationException("GradientDescent computes in fp64 only")
         return self
 
+    multinomialMethod = "auto"
+
+    def setMultinomialMethod(self, method: str) -> "GradientDescent":
+        """The kernels of the batch pass for LogisticGradient(numClasses > 2): "auto" or "mfma"
+        (HipEngine.gradient_sum_multinomial). A binary gradient does not read it."""
+        N.mn_method(method)
+        self.multinomialMethod = method
+        return self
+
     def optimize(self, data: PartitionedData, initialWeights) -> np.ndarray:
-        run = (GradientDescent.runMiniBatchSGDMultinomial if num_classes(self.gradient) > 2
-               else GradientDescent.runMiniBatchSGD)
-        weights, _ = run(
-            data, self.gradient, self.updater, self.stepSize, self.numIterations, self.regParam,
-            self.miniBatchFraction, initialWeights, self.convergenceTol)
+        args = (data, self.gradient, self.updater, self.stepSize, self.numIterations, self.regParam,
+                self.miniBatchFraction, initialWeights, self.convergenceTol)
+        if num_classes(self.gradient) > 2:
+            weights, _ = GradientDescent.runMiniBatchSGDMultinomial(*args, method=self.multinomialMethod)
+        else:
+            weights, _ = GradientDescent.runMiniBatchSGD(*args)
         return weights
 
     @staticmethod
@@ -144,16 +161,18 @@ class GradientDescent(ParallelizedSGD):
     @staticmethod
     def runMiniBatchSGDMultinomial(data: PartitionedData, gradient: Gradient, updater: SGDUpdater, stepSize: float,
                                    numIterations: int, regParam: float, miniBatchFraction: float, initialWeights,
-                                   convergenceTol: float = 0.001, *, engine=None):
+                                   convergenceTol: float = 0.001, *, engine=None, method: str = "auto"):
         """runMiniBatchSGD for LogisticGradient(numClasses = K > 2), the same loop: the weights are
         (K - 1) * num_features doubles (MLlib's require on weights.size), the batch pass is
-        HipEngine.gradient_sum_multinomial. Simple, SquaredL2 and L1 updaters; a binary gradient
-        raises IllegalArgumentException before any device work."""
+        HipEngine.gradient_sum_multinomial with `method`. Simple, SquaredL2 and L1 updaters; a binary
+        gradient raises IllegalArgumentException before any device work."""
         K = _check_multinomial_kinds(gradient, updater)
+        N.mn_method(method)
         return _mini_batch_sgd(data, gradient, updater, stepSize, numIterations, regParam, miniBatchFraction,
                                initialWeights, convergenceTol, engine,
                                lambda nf, size: check_multinomial_weights(K, nf, size), lambda nf: (K - 1) * nf,
-                               lambda eng, w, i: eng.gradient_sum_multinomial(K, w, miniBatchFraction, i))
+                               lambda eng, w, i: eng.gradient_sum_multinomial(K, w, miniBatchFraction, i,
+                                                                              **_method_kw(method)))
 
 
 def _mini_batch_sgd(data, gradient, updater, stepSize, numIterations, regParam, miniBatchFraction, initialWeights,

@@ -712,14 +712,18 @@ class HipEngine(ShardedEngine):
                                lambda w_ptr, out: self.ctx.gradient_sum_device(
                                    kind, w_ptr, miniBatchFraction, iteration, out, self.stream.cuda_stream))
 
-    def gradient_sum_multinomial(self, numClasses: int, w, miniBatchFraction: float = 1.0, iteration: int = 0):
+    def gradient_sum_multinomial(self, numClasses: int, w, miniBatchFraction: float = 1.0, iteration: int = 0,
+                                 method: str = "auto"):
         """gradient_sum() for LogisticGradient(numClasses = K > 2): a device tensor of
         (K - 1) * num_features + 2 doubles {gradientSum, lossSum, count} at the (K - 1) * num_features
-        weights w (psgd_gradient_sum_multinomial_device). The same all-gather and rank-order sums."""
+        weights w (psgd_gradient_sum_multinomial_method_device). The same all-gather and rank-order sums.
+        method: "auto", or "mfma" for the fp64 matrix-core kernels (dense rows, numClasses <= 65,
+        num_features <= 4,096; any other shape raises UnsupportedOperationException)."""
         K = check_num_classes(numClasses)
+        N.mn_method(method)
         return self._batch_sum((K - 1) * self._data.num_features + 2, self._multinomial_weights(K), w,
                                lambda w_ptr, out: self.ctx.gradient_sum_multinomial_device(
-                                   K, w_ptr, miniBatchFraction, iteration, out, self.stream.cuda_stream))
+                                   K, w_ptr, miniBatchFraction, iteration, out, self.stream.cuda_stream, method))
 
     # the augmented Gramian (psgd_gramian_device / psgd_gramian_weighted_device) ------------------
     def local_rows(self) -> int:

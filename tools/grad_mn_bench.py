@@ -20,7 +20,14 @@ each, the ratios of the medians, the bytes of the rows over the time and, for th
 fma count 2 (K - 1) n d (margins and accumulation) over the time beside the vector f64 ceiling of
 tools/multiclass_bench.py (39.3 T fma/s).
 
+--method mfma (dense cases): the fp64 matrix-core path (method="mfma") and the plan's own path ("auto",
+the general or the fused kernel) are timed alternately in the same way, with score_dense_mn and
+project_dense -> f64 rows at k = K - 1 (the multiplier pass's arithmetic without its softmax) beside
+them; the record gives the ratio of the medians and the fma rate against the measured MFMA rate of
+tools/gram_bench.py (39.1 T fma/s).
+
 usage: python tools/grad_mn_bench.py [--what c2,narrow,wide,c4,sweep | all] [--rows N] [--partitions P] [--reps K]
+                                     [--method mfma]
 """
 import argparse
 import json
@@ -32,6 +39,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 F64_FMA_PER_S = 256 * 4 * 16 * 2.4e9   # vector f64 fma a second at the 2.4 GHz peak clock
+MFMA_FMA_PER_S = 39.1e12               # v_mfma_f64_16x16x4_f64 fma a second, measured
 
 
 def timed(st, torch, calls, warmup, reps):
@@ -57,6 +65,8 @@ def main():
     ap.add_argument("--partitions", type=int, default=256)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--method", default="auto", choices=["auto", "mfma"],
+                    help="mfma: time the MFMA path beside the plan's own on the dense cases")
     a = ap.parse_args()
     if a.reps < 20:
         ap.error("--reps must be at least 20")
@@ -68,6 +78,51 @@ def main():
     pkg = g.load_package()
     dev = torch.device("cuda", 0)
     P = a.partitions
+
+    def mfma_case(name, engine, st, K, n, d, nbytes, plan, w, out, o3):
+        mplan = pkg._native.gradient_multinomial_plan("dense", "f32", d, K, method="mfma")
+        k = K - 1
+        ld = k + (k & 1)
+        B = (torch.randn(d, k, dtype=torch.float64, device=dev) / d ** 0.5).contiguous()
+        Y = torch.empty(n, ld, dtype=torch.float64, device=dev)
+        lab = torch.empty(n, dtype=torch.float64, device=dev)
+        rows = [p.n_rows for p in engine._data.partitions]
+        offs = [0]
+        for r in rows:
+            offs.append(offs[-1] + r)
+        y_ptrs = [Y.data_ptr() + o * ld * 8 if r else 0 for o, r in zip(offs, rows)]
+        l_ptrs = [lab.data_ptr() + o * 8 if r else 0 for o, r in zip(offs, rows)]
+
+        def grad(method):
+            engine.ctx.gradient_sum_multinomial_device(K, w.data_ptr(), 1.0, 0, out.data_ptr(), st.cuda_stream, method)
+
+        calls = {"gradient_mn_mfma": lambda: grad("mfma"), "gradient_mn_auto": lambda: grad("auto"),
+                 "score_mn": lambda: engine.ctx.evaluate_multinomial_device(K, w.data_ptr(), o3.data_ptr(),
+                                                                            o3.data_ptr() + 24, st.cuda_stream),
+                 "project_f64": lambda: engine.ctx.project_device(k, B.data_ptr(), 0, ld, y_ptrs, l_ptrs, st.cuda_stream)}
+        torch.cuda.synchronize()
+        ms = timed(st, torch, calls, a.warmup, a.reps)
+        med = {k_: statistics.median(v) for k_, v in ms.items()}
+        rec = {"case": f"{name} K={K}", "auto_path": plan["path"], "mfma_plan": mplan, "rows": n, "features": d,
+               "partitions": P, "reps": a.reps, "bytes": nbytes}
+        for k_, v in ms.items():
+            rec[k_ + "_ms_median"] = round(med[k_], 4)
+            rec[k_ + "_ms_min"] = round(min(v), 4)
+        fma = 2 * (K - 1) * n * d
+        rec["mfma_over_auto"] = round(med["gradient_mn_mfma"] / med["gradient_mn_auto"], 3)
+        rec["mfma_over_score_mn"] = round(med["gradient_mn_mfma"] / med["score_mn"], 3)
+        rec["mfma_over_project_f64"] = round(med["gradient_mn_mfma"] / med["project_f64"], 3)
+        rec["f64_fma"] = fma
+        rec["mfma_Tfma_per_s_median"] = round(fma / med["gradient_mn_mfma"] / 1e9, 2)
+        rec["auto_Tfma_per_s_median"] = round(fma / med["gradient_mn_auto"] / 1e9, 2)
+        rec["mfma_rate_share"] = round(fma / med["gradient_mn_mfma"] / 1e-3 / MFMA_FMA_PER_S, 3)
+        rec["mfma_GBps_median"] = round(nbytes / med["gradient_mn_mfma"] / 1e6, 1)
+        grad("auto")
+        ha = out.cpu().numpy().copy()
+        grad("mfma")
+        hm = out.cpu().numpy()
+        rec["lossSum_mfma"], rec["lossSum_auto"], rec["count"] = float(hm[-2]), float(ha[-2]), int(hm[-1])
+        print(json.dumps(rec), flush=True)
 
     def case(name, parts, layout, n, d, nbytes, classes, max_nnz=0):
         engine = pkg.HipEngine(pkg.PartitionedData(parts))
@@ -92,6 +147,9 @@ def main():
                     os.environ.pop("PSGD_GRAD_MN_TWO_PASS", None)
                 engine.ctx.gradient_sum_multinomial_device(K, w.data_ptr(), 1.0, 0, out.data_ptr(), st.cuda_stream)
 
+            if a.method == "mfma" and layout == "dense":
+                mfma_case(name, engine, st, K, n, d, nbytes, plan, w, out, o3)
+                continue
             calls = {"gradient_mn": lambda: grad_mn(False)}
             if plan["path"] == "fused":
                 calls["gradient_mn_general"] = lambda: grad_mn(True)
