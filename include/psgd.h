@@ -462,6 +462,50 @@ int32_t psgd_gramian_device(psgd_ctx* ctx, double* d_out, void* stream);
 #define PSGD_GRAM_PLAN_LEN 10
 int32_t psgd_gramian_plan(int32_t layout, int32_t storage, int32_t d, int64_t total_tiles, int64_t* out);
 
+/* The tall-skinny QR over every registered row -- the factorisation pass behind MLlib's
+ * RowMatrix.tallSkinnyQR and the numerically sound road to least squares and singular values. With
+ * z_i = [x_i0 .. x_i,d-1, y_i] (a = d + 1 columns; the stored values widened to double, the label as it
+ * is) out receives the a x a upper-triangular R with R^T R = Z^T Z and a non-negative diagonal (with full
+ * column rank that makes R unique): a * a doubles, row-major, the lower triangle zero. So
+ *   R[0..d, 0..d) is the R of X,  R[0..d, d] = Q^T y,  R[d][d] = the least-squares residual norm.
+ * R is built by Householder reflections alone, a panel of 64 rows at a time folded into the R of the
+ * rows before it (LAPACK's dtpqrt, blocked by 16 columns, the trailing updates on
+ * v_mfma_f64_16x16x4_f64); Z^T Z is never formed, so R's error follows cond(Z), not its square. The
+ * reflectors are dlarfg's but for its rescaling of denormal norms: a column that is zero below the
+ * diagonal gives tau = 0, so an all-zero column leaves an exact 0 on R's diagonal and no NaN. All
+ * arithmetic is fp64 whatever the storage. NaN and Inf inputs are outside the contract. The pad columns
+ * of a zero-copy row (ld > d) are never read.
+ * Dense rows with d <= PSGD_TSQR_MAX_D only (R and a panel live in a CU's LDS together): CSR rows and a
+ * wider d are PSGD_EUNSUPPORTED.
+ * Reproducibility: no atomics; the items, the order of their panels and the merge tree are fixed by the
+ * registry's geometry and the plan below (never by the grid): every output has the same bits from call
+ * to call. Registering the same rows as more or fewer partitions changes the tiling and so the last bits.
+ * Errors: PSGD_EINVAL for a null ctx or pointer; PSGD_ESTATE when no partition is registered. A
+ * registry of empty partitions gives zeros. Streams, ordering and scratch are psgd_gramian's.
+ *
+ * psgd_tsqr_rows_device is the same factorisation over n caller-given rows of a doubles on the device
+ * (row-major, no label column, a <= PSGD_TSQR_MAX_D + 1; d_out receives a * a doubles): the entry point of
+ * the merge -- stacking the R factors of several ranks and factoring the stack gives the R of all their
+ * rows. It needs no registered partition; n = 0 gives zeros. PSGD_EINVAL for n < 0 or a < 1. */
+#define PSGD_TSQR_MAX_D 127
+int32_t psgd_tsqr(psgd_ctx* ctx, double* out);
+int32_t psgd_tsqr_device(psgd_ctx* ctx, double* d_out, void* stream);
+int32_t psgd_tsqr_rows_device(psgd_ctx* ctx, const double* d_rows, int64_t n, int32_t a, double* d_out, void* stream);
+
+/* How psgd_tsqr runs dense rows of `storage` (psgd_dtype) and d features cut into total_tiles tiles of
+ * the statistics passes: host code, no device and no context. out[PSGD_TSQR_PLAN_LEN] receives
+ *   [0] a = d + 1; [1] a_pad, a rounded up to whole blocks of 16 columns;
+ *   [2] the work items, [3] the consecutive tiles an item spans: one workgroup an item;
+ *   [4] rows of a panel;
+ *   [5] the merge tree's fan-in, [6] its levels, ceil(log_fan(items)): the tree follows from [2] alone;
+ *   [7] bytes of LDS a workgroup takes (R's blocks on and above the diagonal, the panel, V2^T and Tf);
+ *   [8] bytes of scratch, items * a_pad^2 doubles (a merge node writes into its first child's slot);
+ *   [9] rows of a tile.
+ * Errors: PSGD_EINVAL for a null out, an unknown storage, d <= 0 or total_tiles < 0; PSGD_EUNSUPPORTED
+ * for d > PSGD_TSQR_MAX_D. */
+#define PSGD_TSQR_PLAN_LEN 10
+int32_t psgd_tsqr_plan(int32_t storage, int32_t d, int64_t total_tiles, int64_t* out);
+
 /* The number of registered rows: the length of the per-row arrays below. Their order is local row
  * order: the registered partitions in partition-index order, a partition's rows in iterator order.
  * Errors: PSGD_EINVAL for a null ctx or out. */

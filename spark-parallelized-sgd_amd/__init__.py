@@ -25,8 +25,8 @@ from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdate
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
 from .split import kFold, randomSplit
-from .stat import (Gramian, MultivariateGaussian, computePrincipalComponents, computeSVD, corr, covariance, gramian,
-                   multiply, normal_equations)
+from .stat import (Gramian, MultivariateGaussian, QRDecomposition, QRFactor, computePrincipalComponents, computeSVD,
+                   corr, covariance, gramian, least_squares, multiply, normal_equations, qr_factor, tallSkinnyQR)
 from .util import loadLibSVMFile
 
 __all__ = [
@@ -38,6 +38,7 @@ __all__ = [
     "KMeans", "KMeansModel", "KMeansStep", "kmeans_step",
     "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureStep", "gmm_step", "MultivariateGaussian",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
+    "QRFactor", "QRDecomposition", "qr_factor", "least_squares", "tallSkinnyQR",
     "multiply", "computePrincipalComponents", "computeSVD", "PCA", "PCAModel",
     "column_stats", "ColumnStats", "StandardScaler", "StandardScalerModel", "ShardedEngine", "make_params",
     "Gradient", "LogisticGradient", "LeastSquaresGradient", "HingeGradient",

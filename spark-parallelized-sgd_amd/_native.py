@@ -37,6 +37,7 @@ EXPORTED = (
     "psgd_gradient_multinomial_plan_method",
     "psgd_gramian", "psgd_gramian_device", "psgd_gramian_plan",
     "psgd_gramian_weighted", "psgd_gramian_weighted_device", "psgd_local_rows",
+    "psgd_tsqr", "psgd_tsqr_device", "psgd_tsqr_rows_device", "psgd_tsqr_plan",
     "psgd_row_curvature", "psgd_row_curvature_device",
     "psgd_project", "psgd_project_device", "psgd_project_plan",
     "psgd_kmeans_assign", "psgd_kmeans_assign_device", "psgd_kmeans_step", "psgd_kmeans_step_device",
@@ -163,6 +164,10 @@ def lib():
             "psgd_gramian_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
             "psgd_gramian_weighted": ([vp, vp, vp], C.c_int32),
             "psgd_gramian_weighted_device": ([vp, vp, vp, vp], C.c_int32),
+            "psgd_tsqr": ([vp, vp], C.c_int32),
+            "psgd_tsqr_device": ([vp, vp, vp], C.c_int32),
+            "psgd_tsqr_rows_device": ([vp, vp, C.c_int64, C.c_int32, vp, vp], C.c_int32),
+            "psgd_tsqr_plan": ([C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
             "psgd_local_rows": ([vp, vp], C.c_int32),
             "psgd_row_curvature": ([vp, C.c_int32, vp, vp], C.c_int32),
             "psgd_row_curvature_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
@@ -357,6 +362,19 @@ def gramian_plan(layout: str, storage: str, d: int, total_tiles: int) -> dict:
     plan = {k: int(v) for k, v in zip(keys, out)}
     plan["path"] = ("dense_mfma", "csr")[plan["path"]]
     return plan
+
+
+TSQR_MAX_D = 127   # PSGD_TSQR_MAX_D
+
+
+def tsqr_plan(storage: str, d: int, total_tiles: int) -> dict:
+    """How psgd_tsqr runs dense rows stored as `storage` ("f32" / "f64") with d features cut into
+    total_tiles tiles (psgd_tsqr_plan: host code, no device)."""
+    out = (C.c_int64 * 10)()
+    check(lib().psgd_tsqr_plan({"f64": 0, "f32": 1}[storage], int(d), int(total_tiles), out))
+    keys = ("a", "a_pad", "items", "span_tiles", "panel_rows", "fan_in", "levels", "lds_bytes", "scratch_bytes",
+            "tile_rows")
+    return {k: int(v) for k, v in zip(keys, out)}
 
 
 class _PinnedBuffer:
@@ -645,6 +663,23 @@ class Context:
         n = C.c_int64()
         check(self._L.psgd_local_rows(self.handle, C.byref(n)))
         return int(n.value)
+
+    # the tall-skinny QR ---------------------------------------------------------------------------
+    def tsqr(self, d: int):
+        """Host-pointer form (psgd_tsqr): the upper-triangular R of Z = [x, y] as a (d + 1, d + 1) array."""
+        import numpy as np
+        a = int(d) + 1
+        out = np.empty((a, a), dtype=np.float64)
+        check(self._L.psgd_tsqr(self.handle, out.ctypes.data))
+        return out
+
+    def tsqr_device(self, out_ptr, stream=None):
+        """psgd_tsqr_device: enqueued on `stream`; out[(d + 1)^2] on the device."""
+        check(self._L.psgd_tsqr_device(self.handle, out_ptr, stream))
+
+    def tsqr_rows_device(self, rows_ptr, n: int, a: int, out_ptr, stream=None):
+        """psgd_tsqr_rows_device: the R of rows[n, a] (f64, on the device) into out[a^2]."""
+        check(self._L.psgd_tsqr_rows_device(self.handle, rows_ptr, int(n), int(a), out_ptr, stream))
 
     def gramian_weighted(self, d: int, omega):
         """Host-pointer form (psgd_gramian_weighted): M_w = sum omega_i z_i z_i^T, omega one double per

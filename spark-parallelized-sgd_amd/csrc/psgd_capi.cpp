@@ -2688,6 +2688,100 @@ int32_t psgd_gramian_weighted(psgd_ctx* ctx, const double* omega, double* out) {
     return gramian_host(ctx, omega, out);
 }
 
+// ---- The tall-skinny QR (kernels in psgd_tsqr.hip) ----
+// The same place in the context as the Gramian: score_prepare, the Gramian's scratch, no epoch state touched.
+static int32_t tsqr_serves(int32_t layout, int32_t d) {
+    if (layout == psgd::kCsr) return fail(PSGD_EUNSUPPORTED, "the tall-skinny QR needs dense rows (the partitions are CSR)");
+    if (d > PSGD_TSQR_MAX_D)
+        return fail(PSGD_EUNSUPPORTED, "the tall-skinny QR of d = " + std::to_string(d) + " features exceeds the built maximum of " +
+                                           std::to_string(PSGD_TSQR_MAX_D) + " features (R lives in LDS)");
+    return PSGD_OK;
+}
+
+int32_t psgd_tsqr_device(psgd_ctx* ctx, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_out) return fail(PSGD_EINVAL, "d_out is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    const Part& first = ctx->parts.begin()->second;
+    int32_t rc = tsqr_serves(first.layout, first.d);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const int storage = first.dtype == PSGD_F32 ? 1 : 0;
+    const int64_t n_tiles = ctx->stat_tile0.back();
+    const psgd::TsqrGeom gm = psgd::tsqr_geometry(storage, first.d, n_tiles);
+    HIP_TRY(ctx->qrec.ensure((size_t)gm.scratch_bytes + sizeof(double)));
+    const int e = psgd::launch_tsqr(ctx->descs.as<psgd::ChainDesc>(), ctx->stile0.as<int64_t>(), (int)ctx->parts.size(),
+                                    n_tiles, gm, storage, ctx->qrec.as<double>(), d_out, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tall-skinny QR launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tsqr(psgd_ctx* ctx, double* out) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    size_t len = 0;
+    double* d_out = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        const Part& first = ctx->parts.begin()->second;
+        int32_t rc = tsqr_serves(first.layout, first.d);
+        if (rc) return rc;
+        len = ((size_t)first.d + 1) * ((size_t)first.d + 1);
+        DeviceGuard g(ctx->device);
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        HIP_TRY(ctx->qio.ensure(len * sizeof(double)));
+        d_out = ctx->qio.as<double>();
+    }
+    int32_t rc = psgd_tsqr_device(ctx, d_out, ctx->stream);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(out, d_out, len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_tsqr_rows_device(psgd_ctx* ctx, const double* d_rows, int64_t n, int32_t a, double* d_out, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (n < 0) return fail(PSGD_EINVAL, "n must be >= 0");
+    if (a < 1) return fail(PSGD_EINVAL, "a must be positive");
+    if (a > PSGD_TSQR_MAX_D + 1)
+        return fail(PSGD_EUNSUPPORTED, "the tall-skinny QR takes at most " + std::to_string(PSGD_TSQR_MAX_D + 1) +
+                                           " columns (got " + std::to_string(a) + ")");
+    if (!d_out || (n > 0 && !d_rows)) return fail(PSGD_EINVAL, "d_rows/d_out are null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int32_t rc = scratch_acquire(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const psgd::TsqrGeom gm = psgd::tsqr_rows_geometry(a, n);
+    HIP_TRY(ctx->qrec.ensure((size_t)gm.scratch_bytes + sizeof(double)));
+    const int e = psgd::launch_tsqr_rows(d_rows, n, gm, ctx->qrec.as<double>(), d_out, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tall-skinny QR launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tsqr_plan(int32_t storage, int32_t d, int64_t total_tiles, int64_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
+    if (d <= 0) return fail(PSGD_EINVAL, "d must be positive");
+    if (total_tiles < 0) return fail(PSGD_EINVAL, "total_tiles must be >= 0");
+    const int32_t rc = tsqr_serves(psgd::kDense, d);
+    if (rc) return rc;
+    const psgd::TsqrGeom gm = psgd::tsqr_geometry(storage == PSGD_F32 ? 1 : 0, d, total_tiles);
+    const int64_t v[PSGD_TSQR_PLAN_LEN] = {gm.a,   gm.a_pad,  gm.items,     gm.span,          gm.panel_rows,
+                                           gm.fan, gm.levels, gm.lds_bytes, gm.scratch_bytes, gm.tile_rows};
+    std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
 int32_t psgd_local_rows(psgd_ctx* ctx, int64_t* out) {
     if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
     if (!out) return fail(PSGD_EINVAL, "out is null");

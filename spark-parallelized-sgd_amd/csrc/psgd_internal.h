@@ -391,6 +391,31 @@ int launch_gramian_csr(const ChainDesc* descs, const int64_t* tile0, int n_parts
                        const GramGeom& gm, int storage, double* rec, double* out, int num_cus, hipStream_t st,
                        const double* omega = nullptr, const int64_t* row0 = nullptr);
 
+// ---- The tall-skinny QR (psgd_tsqr.hip: psgd_tsqr) ----
+// The plan of a call: host code, no device (psgd_tsqr_plan reports it). An item is a span of `span`
+// consecutive tiles of the statistics passes' tiling (tsqr_geometry), or tile_rows consecutive rows of a
+// caller's f64 array (tsqr_rows_geometry); the items' R factors are merged by a tree of fan-in `fan` and
+// `levels` levels whose shape follows from `items` alone.
+struct TsqrGeom {
+    int32_t d, a, nb, a_pad;   // features, columns of Z (d + 1; the rows form: a = d), blocks of 16, 16 nb
+    int32_t pitch;             // the panel's pitch in LDS, doubles
+    int32_t panel_rows;        // rows of a panel
+    int32_t fan, levels;
+    int32_t tile_rows;
+    int64_t span, items;
+    int64_t lds_bytes;         // a workgroup's LDS: R's blocks, the panel, V2^T and Tf
+    int64_t scratch_bytes;     // items * a_pad^2 doubles
+};
+TsqrGeom tsqr_geometry(int storage, int d, int64_t n_tiles);
+TsqrGeom tsqr_rows_geometry(int a, int64_t n_rows);
+// out[a * a] = R (row-major, upper triangular, diagonal >= 0) of Z = [X, y] over the dense rows of
+// descs[0 .. n_parts); scratch is gm.scratch_bytes. No atomics, reproducible bits; zeros without rows.
+int launch_tsqr(const ChainDesc* descs, const int64_t* tile0, int n_parts, int64_t n_tiles, const TsqrGeom& gm,
+                int storage, double* scratch, double* out, hipStream_t st);
+// The same over rows[n_rows * a] (device, f64, row-major, no label column); gm = tsqr_rows_geometry.
+int launch_tsqr_rows(const double* rows, int64_t n_rows, const TsqrGeom& gm, double* scratch, double* out,
+                     hipStream_t st);
+
 // ---- The rows' curvature (psgd_hessian.hip: psgd_row_curvature) ----
 // out[row0[p] + r] = d^2 loss / d(x . w)^2 of row r of partition p at weights w[d], over the scoring
 // passes' tiling (EvalPart), n_rows rows in all. gradient: G_LOGISTIC or G_LEAST_SQUARES.

@@ -750,6 +750,45 @@ class HipEngine(ShardedEngine):
         return self._batch_sum((nf + 2) * (nf + 2), self._row_weights, weights,
                                lambda om, out: self.ctx.gramian_weighted_device(om, out, self.stream.cuda_stream))
 
+    # the tall-skinny QR (psgd_tsqr_device / psgd_tsqr_rows_device) ---------------------------------
+    def tsqr(self):
+        """The upper-triangular R (diagonal >= 0) with R^T R = Z^T Z, Z = [x, y], over every row of the
+        data, on all ranks, as a device tensor of (d + 1)^2 doubles, row-major (include/psgd.h has the
+        semantics; stat.QRFactor reads it). Each rank factors its partitions; with more than one rank
+        the ranks all-gather their R factors (the backends of exchange()) and every rank factors the
+        stack in rank order with psgd_tsqr_rows_device, so all ranks hold the same bits; a rank without
+        partitions contributes zeros. Dense rows with at most TSQR_MAX_D features only."""
+        torch = self.torch
+        nf = self._data.num_features
+        if self._data.partitions and isinstance(self._data.partitions[0], (CsrPartition, DeviceCsrPartition)):
+            raise N.UnsupportedOperationException("the tall-skinny QR needs dense rows (the partitions are CSR)")
+        if nf > N.TSQR_MAX_D:
+            raise N.UnsupportedOperationException(
+                f"the tall-skinny QR takes at most {N.TSQR_MAX_D} features (got {nf}): R lives in LDS")
+        a = nf + 1
+        buf = self._batch_sum(a * a, None, None,
+                              lambda _w, out: self.ctx.tsqr_device(out, self.stream.cuda_stream), local=True)
+        if self.world == 1:
+            return buf
+        import torch.distributed as dist
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            if dist.get_backend() == "gloo":   # (through the host: a * a doubles a rank)
+                mine = buf.cpu()
+                parts = [torch.empty_like(mine) for _ in range(self.world)]
+                dist.all_gather(parts, mine)
+                got = torch.cat(parts).to(self.dev)
+            else:
+                got = torch.empty(self.world * a * a, dtype=torch.float64, device=self.dev)
+                dist.all_gather_into_tensor(got, buf)
+            out = torch.zeros(a * a, dtype=torch.float64, device=self.dev)
+            with self.ctx.engine_lock:
+                self.ctx.tsqr_rows_device(got.data_ptr(), self.world * a, a, out.data_ptr(), self.stream.cuda_stream)
+        self.stream.synchronize()   # got is a temporary of this call
+        out.record_stream(caller)
+        return out
+
     def device_rows(self, values):
         """A host array of local_rows() doubles as a device tensor (gramian()'s weights)."""
         with self.torch.cuda.stream(self.stream):

@@ -19,6 +19,12 @@ host over a (d + 2) x (d + 2) array, so `Gramian` can be built from any such arr
 the one function here that writes rows: Y = X B on the device (fp64 MFMA over dense rows,
 HipEngine.project), the rows' labels kept beside them.
 
+  f = qr_factor(data)                # one pass: the R of [X, y] by Householder reflections (HipEngine.tsqr)
+  f.R, f.qty, f.residualNorm         # the R of X, Q^T y, ||X w* - y||
+  w_star = f.least_squares(0.1)      # normal_equations' minimiser without X^T X: the error follows cond(X)
+  s, V = f.svd(k)                    # singular values down to eps * sigma_0, not sqrt(eps) * sigma_0
+  Q, R = tallSkinnyQR(data, computeQ=True)    # RowMatrix.tallSkinnyQR
+
 The definitions are this project's restatement of MLlib 1.6.1 (RowMatrix.computeCovariance,
 PearsonCorrelation, RowMatrix.multiply / computePrincipalComponents / computeSVD), not pinned to its
 source. Two things are this project's own: the sign of a principal component or singular vector is
@@ -29,7 +35,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from ._native import PROJECT_MAX_K, IllegalArgumentException
+import collections
+
+from ._native import PROJECT_MAX_K, IllegalArgumentException, UnsupportedOperationException
 from .data import PartitionedData
 
 
@@ -314,6 +322,128 @@ def computeSVD(data: PartitionedData, k, computeU: bool = False, rCond: float = 
     s, V = gramian(data, engine=engine).svd(k, rCond)
     U = multiply(data, V / s[None, :], "f64", engine=engine) if computeU else None
     return U, s, V
+
+
+class QRFactor:
+    """A host object over the upper-triangular R of Z = [X, y] (R^T R = Z^T Z, diagonal >= 0), a
+    (d + 1) x (d + 1) array of doubles, and the row count n. R is the leading d x d block (the R of X), qty
+    its last column above the corner (Q^T y), residualNorm the corner (the least-squares residual norm)."""
+
+    def __init__(self, matrix, count: int):
+        m = np.array(matrix, dtype=np.float64)
+        if m.ndim == 1:
+            a = int(round(np.sqrt(m.size)))
+            m = m.reshape(a, a) if a * a == m.size else m
+        if m.ndim != 2 or m.shape[0] != m.shape[1] or m.shape[0] < 2:
+            raise IllegalArgumentException(
+                f"requirement failed: the R of [X, y] is (d + 1) x (d + 1) with d >= 1 (got shape {m.shape})")
+        self.matrix = np.triu(m)
+        self.d = m.shape[0] - 1
+        self.count = int(count)
+
+    @property
+    def R(self) -> np.ndarray:
+        return self.matrix[: self.d, : self.d]
+
+    @property
+    def qty(self) -> np.ndarray:
+        return self.matrix[: self.d, self.d]
+
+    @property
+    def residualNorm(self) -> float:
+        return float(self.matrix[self.d, self.d])
+
+    def least_squares(self, regParam: float = 0.0) -> np.ndarray:
+        """The minimiser Gramian.normal_equations documents, (1 / n) sum (w . x - y)^2 / 2 + (regParam / 2)
+        ||w||^2, without X^T X: the R of [[R, qty], [sqrt(n regParam) I, 0]] (numpy.linalg.qr on the host),
+        then a triangular solve. With regParam = 0 a diagonal entry of R at or below d * eps * max|diag|
+        raises normal_equations' message."""
+        lam = float(regParam)
+        if not lam >= 0.0:
+            raise IllegalArgumentException(f"requirement failed: regParam must be nonnegative but got {regParam}")
+        if self.count <= 0:
+            raise IllegalArgumentException("requirement failed: the normal equations need at least one row")
+        d = self.d
+        top = self.matrix[:d, :]
+        if lam > 0.0:
+            low = np.hstack([np.sqrt(self.count * lam) * np.eye(d), np.zeros((d, 1))])
+            top = np.linalg.qr(np.vstack([top, low]), mode="r")[:d, :]
+        diag = np.abs(np.diag(top[:, :d]))
+        if not np.all(diag > d * np.finfo(np.float64).eps * np.max(diag)):
+            raise IllegalArgumentException(
+                "requirement failed: X^T X / n + regParam I is not positive definite (collinear or constant-zero "
+                "columns): use regParam > 0 or drop the dependent columns")
+        w = np.array(top[:, d])
+        for j in range(d - 1, -1, -1):   # back substitution
+            w[j] = (w[j] - top[j, j + 1: d] @ w[j + 1:]) / top[j, j]
+        return w
+
+    def svd(self, k, rCond: float = 1e-9):
+        """RowMatrix.computeSVD(k, rCond = rCond) from numpy.linalg.svd(R): (s, V) with Gramian.svd's sign
+        convention and rCond rule. The singular values are R's own, so there is no 1e-8 sigma_0 floor."""
+        k = _check_k(k, self.d, "computeSVD")
+        if not 0.0 <= float(rCond) <= 1.0:
+            raise IllegalArgumentException(f"requirement failed: rCond must be within [0, 1] but got {rCond}")
+        _, sigma, Vt = np.linalg.svd(self.R)
+        if not sigma[0] > 0.0:
+            raise IllegalArgumentException("requirement failed: computeSVD needs a matrix with a non-zero entry")
+        keep = 0
+        while keep < k and sigma[keep] > float(rCond) * sigma[0]:
+            keep += 1
+        return sigma[:keep].copy(), np.ascontiguousarray(_fix_signs(Vt.T[:, :keep]))
+
+    def __repr__(self) -> str:
+        return f"QRFactor(d={self.d}, count={self.count})"
+
+
+QRDecomposition = collections.namedtuple("QRDecomposition", ["Q", "R"])
+
+
+def qr_factor(data: PartitionedData, *, engine=None) -> QRFactor:
+    """The R of [X, y] over every row of every partition, on all ranks (HipEngine.tsqr): one pass of
+    Householder reflections on the device, fp64. Dense rows with at most TSQR_MAX_D features (CSR rows
+    and a wider d raise UnsupportedOperationException); data without rows raises, as gramian does."""
+    from . import _native as N
+    from .data import CsrPartition, DeviceCsrPartition
+    if data.num_partitions == 0 or data.count() == 0:
+        raise IllegalArgumentException("requirement failed: Cannot compute the QR factorisation of data without rows.")
+    if isinstance(data.partitions[0], (CsrPartition, DeviceCsrPartition)):
+        raise UnsupportedOperationException("the tall-skinny QR needs dense rows (the partitions are CSR)")
+    if data.num_features > N.TSQR_MAX_D:
+        raise UnsupportedOperationException(
+            f"the tall-skinny QR takes at most {N.TSQR_MAX_D} features (got {data.num_features}): R lives in LDS")
+    if engine is None:
+        from .optimization import HipEngine, _dist
+        rank, world, _ = _dist()
+        engine = HipEngine(data, rank, world)
+    a = data.num_features + 1
+    return QRFactor(engine.tsqr().cpu().numpy().reshape(a, a), data.count())
+
+
+def least_squares(data: PartitionedData, regParam: float = 0.0, *, engine=None) -> np.ndarray:
+    """normal_equations' minimiser through the QR factorisation (QRFactor.least_squares)."""
+    if not float(regParam) >= 0.0:
+        raise IllegalArgumentException(f"requirement failed: regParam must be nonnegative but got {regParam}")
+    return qr_factor(data, engine=engine).least_squares(regParam)
+
+
+def tallSkinnyQR(data: PartitionedData, computeQ: bool = False, *, engine=None) -> QRDecomposition:
+    """RowMatrix.tallSkinnyQR(computeQ): QRDecomposition(Q, R) with R (d x d) the R of X, its diagonal
+    non-negative (this project's convention; MLlib leaves the sign to LAPACK), and Q = X R^-1 as multiply
+    returns it in f64 (MLlib's own way to Q), or None. A singular R raises when computeQ is set."""
+    if engine is None and data.num_partitions and data.count():
+        from .optimization import HipEngine, _dist
+        rank, world, _ = _dist()
+        engine = HipEngine(data, rank, world)
+    R = np.ascontiguousarray(qr_factor(data, engine=engine).R)
+    if not computeQ:
+        return QRDecomposition(None, R)
+    diag = np.abs(np.diag(R))
+    if not np.all(diag > R.shape[0] * np.finfo(np.float64).eps * np.max(diag)):
+        raise IllegalArgumentException("requirement failed: R is singular (collinear or constant-zero columns): Q = X R^-1 "
+                                       "does not exist")
+    Rinv = np.linalg.solve(R, np.eye(R.shape[0]))
+    return QRDecomposition(multiply(data, Rinv, "f64", engine=engine), R)
 
 
 class MultivariateGaussian:
