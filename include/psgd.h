@@ -655,6 +655,87 @@ int32_t psgd_kmeans_update_device(psgd_ctx* ctx, int32_t k, int32_t d, const dou
 #define PSGD_KMEANS_PLAN_LEN 12
 int32_t psgd_kmeans_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, int64_t total_tiles, int64_t* out);
 
+/* A decision-tree classifier over every registered row -- the passes behind DecisionTree.trainClassifier
+ * for dense rows with continuous features, trained level by level. This is the project's restatement of
+ * MLlib 1.6.1's model, not pinned to its source. All counts are exact integers.
+ * Thresholds: feature f has nb_f <= max_bins <= PSGD_TREE_MAX_BINS bins, separated by nb_f - 1 strictly
+ *   ascending doubles T_f (thresholds[f * (max_bins - 1) + j], j < nbins[f] - 1; the rest is not read).
+ *   bin(x) = the number of thresholds t with x > t, the stored value widened to f64 first: x <= T[0] is
+ *   bin 0. NaN is outside the contract.
+ * Binned rows: bytes bins[r][f], row-major at a pitch of d rounded up to 16; the pad bytes are 0 and are
+ *   never counted; rows in local row order (psgd_row_curvature's). Beside them one label byte a row: the
+ *   label when it is a whole number in [0, 255), else 255. Both are the caller's device buffers.
+ * Frontier: the nodes a level may split are numbered 0 .. A - 1 ("slots"); slot[r] (int32) is the row's
+ *   slot, or -1 once the row sits in a finished leaf.
+ * Histogram: H[slot][f][b][c] (64-bit, the pitches are max_bins and num_classes) = the local rows with that
+ *   slot, bins[r][f] = b and label c, for the slots slot0 .. slot0 + n_slots - 1; the call zeroes the table
+ *   first. 2 <= num_classes <= PSGD_TREE_MAX_CLASSES; a row of those slots whose label byte is >=
+ *   num_classes adds 1 to *d_nbad (the caller zeroes it) and to no cell. Integer adds in LDS (uint32),
+ *   integer atomics into H: exact in any order, so ranks may add their tables in any order too.
+ *   replication: 0 the plan's choice, 1 one copy of the LDS sub-table, 2 one for odd and one for even rows.
+ * Best split of a slot: tot[c] = sum_b H[slot][0][b][c], n = sum tot. For feature f and candidate b in
+ *   [0, nb_f - 2]: L[c] = sum_{b' <= b} H[slot][f][b'][c], R = tot - L; valid when nL >= min_instances and
+ *   nR >= min_instances; gain = imp(tot) - (nL / n) imp(L) - (nR / n) imp(R), with gini = 1 - sum_c (c / n)^2
+ *   and entropy = - sum_c (c / n) ln(c / n) / ln 2 (0 for an empty class), all fp64, the classes in index
+ *   order. The winner is the valid candidate of largest gain, ties to the lowest feature, then the lowest
+ *   bin. The slot is a leaf when no candidate is valid or the best gain is <= 0 or < min_info_gain.
+ *   d_rec[slot] holds 6 + 2 num_classes doubles: feature (-1: a leaf), bin, threshold, gain (the best valid
+ *   candidate's, 0 without one), imp(tot), n, tot[], L[] (zeros for a leaf).
+ * Routing: d_table[slot] = {feature, bin, left slot, right slot} (int32 x 4). A row of a slot with
+ *   feature >= 0 goes left when bins[r][feature] <= bin; its slot becomes the child's (-1: the child is a
+ *   finished leaf). A row of a slot with feature < 0 or past the table gets -1.
+ * Prediction: node arrays of n_nodes entries on the host, node 0 the root, feature < 0 a leaf, the children
+ *   of a node later in the arrays; from the root go left while (double)x[feature] <= threshold. Writes the
+ *   leaf's prediction (int32) and, when asked, its probability, in local row order. This agrees with the
+ *   bins by construction when the thresholds are the bins' own.
+ * Errors: PSGD_EINVAL for a null ctx or pointer (d_prob / prob may be null), thresholds that do not ascend
+ *   strictly, nbins outside [1, max_bins], max_bins < 2, num_classes < 2, d_bins or d_table off a 16-byte
+ *   boundary, an unknown impurity, min_instances < 1, a negative min_info_gain or a node whose feature or
+ *   children are out of range; PSGD_EUNSUPPORTED for CSR partitions, num_classes > PSGD_TREE_MAX_CLASSES and
+ *   max_bins > PSGD_TREE_MAX_BINS; PSGD_ESTATE when no partition is registered. Every output has the same
+ *   bits from call to call. The calls only read the rows; like the scoring calls they wait for registration
+ *   copies in flight and leave the epoch state alone. */
+#define PSGD_TREE_MAX_BINS 256
+#define PSGD_TREE_MAX_CLASSES 32
+#define PSGD_TREE_SCRATCH_BUDGET (256ll << 20)
+#define PSGD_TREE_GINI 0
+#define PSGD_TREE_ENTROPY 1
+int32_t psgd_tree_bin_device(psgd_ctx* ctx, const double* thresholds, const int32_t* nbins, int32_t max_bins,
+                             double* d_thresholds, int32_t* d_nbins, uint8_t* d_bins, uint8_t* d_labels, void* stream);
+int32_t psgd_tree_histogram_device(psgd_ctx* ctx, const uint8_t* d_bins, const uint8_t* d_labels, const int32_t* d_slot,
+                                   int32_t num_classes, int32_t max_bins, int32_t slot0, int32_t n_slots,
+                                   int32_t replication, int64_t* d_hist, int64_t* d_nbad, void* stream);
+int32_t psgd_tree_best_split_device(psgd_ctx* ctx, const int64_t* d_hist, const double* d_thresholds, const int32_t* d_nbins,
+                                    int32_t d, int32_t max_bins, int32_t num_classes, int32_t n_slots, int32_t impurity,
+                                    int64_t min_instances, double min_info_gain, double* d_rec, void* stream);
+int32_t psgd_tree_route_device(psgd_ctx* ctx, const uint8_t* d_bins, const int32_t* d_table, int32_t n_table, int32_t* d_slot,
+                               void* stream);
+int32_t psgd_tree_predict(psgd_ctx* ctx, int32_t n_nodes, const int32_t* feature, const double* threshold, const int32_t* left,
+                          const int32_t* right, const int32_t* prediction, const double* probability, int32_t* classes,
+                          double* prob);
+int32_t psgd_tree_predict_device(psgd_ctx* ctx, int32_t n_nodes, const int32_t* feature, const double* threshold,
+                                 const int32_t* left, const int32_t* right, const int32_t* prediction,
+                                 const double* probability, int32_t* d_classes, double* d_prob, void* stream);
+
+/* How psgd_tree_histogram_device runs a frontier of `slots` slots over rows of d features cut into
+ * total_tiles tiles of 256 local rows: host code, no device and no context (the storage of the rows does
+ * not enter: the pass reads the binned bytes). budget: the bytes the 64-bit table of one launch may take
+ * (<= 0: PSGD_TREE_SCRATCH_BUDGET); a larger frontier is processed in groups of slots, one launch each.
+ * out[PSGD_TREE_PLAN_LEN] receives
+ *   [0] the feature chunk of a work item: whole 16-byte vectors of 16 features, or 1, 2, 4 or 8 features
+ *       when 16 features' cells exceed the LDS table;
+ *   [1] the slot sub-group: the slots a work item counts;
+ *   [2] the replication: copies of the sub-table in LDS (2 when every feature and slot of a group fit twice);
+ *   [3] bytes of dynamic LDS of the launch (64 KiB at most: two workgroups share a CU);
+ *   [4] the groups of a level; [5] bytes of the 64-bit table of a group; [6] the slots of a group;
+ *   [7] the work items of a launch (spans x feature chunks x sub-groups); [8] the rows of a span;
+ *   [9] the pitch of a binned row in bytes.
+ * Errors: PSGD_EINVAL for a null out, an unknown storage, d <= 0, slots < 1, total_tiles < 0, max_bins < 2 or
+ * num_classes < 2; PSGD_EUNSUPPORTED past PSGD_TREE_MAX_BINS / PSGD_TREE_MAX_CLASSES. */
+#define PSGD_TREE_PLAN_LEN 10
+int32_t psgd_tree_plan(int32_t storage, int32_t d, int32_t max_bins, int32_t num_classes, int32_t slots, int64_t total_tiles,
+                       int64_t budget, int64_t* out);
+
 /* One EM step of a Gaussian mixture over every registered row -- the passes behind MLlib 1.6.1's
  * GaussianMixture and GaussianMixtureModel.predictSoft. Dense rows only. A model is k components
  * (w_j, mu_j, Sigma_j), 1 <= k <= PSGD_GMM_MAX_K, over d <= PSGD_GMM_MAX_D features. The host prepares,

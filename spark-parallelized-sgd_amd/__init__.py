@@ -21,6 +21,7 @@ from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradi
 from .newton import HessianSum, Newton, hessian_sum, runNewton
 from .clustering import (GaussianMixture, GaussianMixtureModel, GaussianMixtureStep, KMeans, KMeansModel, KMeansStep,
                          gmm_step, kmeans_step)
+from .tree import DecisionTree, DecisionTreeModel, TreeBins, find_splits
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
@@ -37,6 +38,7 @@ __all__ = [
     "Newton", "runNewton", "hessian_sum", "HessianSum",
     "KMeans", "KMeansModel", "KMeansStep", "kmeans_step",
     "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureStep", "gmm_step", "MultivariateGaussian",
+    "DecisionTree", "DecisionTreeModel", "TreeBins", "find_splits",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
     "QRFactor", "QRDecomposition", "qr_factor", "least_squares", "tallSkinnyQR",
     "multiply", "computePrincipalComponents", "computeSVD", "PCA", "PCAModel",

@@ -42,6 +42,8 @@ EXPORTED = (
     "psgd_project", "psgd_project_device", "psgd_project_plan",
     "psgd_kmeans_assign", "psgd_kmeans_assign_device", "psgd_kmeans_step", "psgd_kmeans_step_device",
     "psgd_kmeans_update_device", "psgd_kmeans_plan",
+    "psgd_tree_bin_device", "psgd_tree_histogram_device", "psgd_tree_best_split_device", "psgd_tree_route_device",
+    "psgd_tree_predict", "psgd_tree_predict_device", "psgd_tree_plan",
     "psgd_gmm_responsibilities", "psgd_gmm_responsibilities_device", "psgd_gmm_moments_device",
     "psgd_gmm_step", "psgd_gmm_step_device", "psgd_gmm_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
@@ -180,6 +182,15 @@ def lib():
             "psgd_kmeans_step_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
             "psgd_kmeans_update_device": ([vp, C.c_int32, C.c_int32, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_kmeans_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, vp], C.c_int32),
+            "psgd_tree_bin_device": ([vp, vp, vp, C.c_int32, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_tree_histogram_device": ([vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                            vp], C.c_int32),
+            "psgd_tree_best_split_device": ([vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int64, C.c_double, vp, vp], C.c_int32),
+            "psgd_tree_route_device": ([vp, vp, vp, C.c_int32, vp, vp], C.c_int32),
+            "psgd_tree_predict": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_tree_predict_device": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
+            "psgd_tree_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, vp], C.c_int32),
             "psgd_gmm_responsibilities": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_gmm_responsibilities_device": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_gmm_moments_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
@@ -331,6 +342,23 @@ def kmeans_plan(layout: str, storage: str, d: int, k: int, total_tiles: int) -> 
     plan = {k_: int(v) for k_, v in zip(keys, out)}
     plan["path"] = KMEANS_PATHS[plan["path"]]
     return plan
+
+
+TREE_MAX_BINS = 256       # PSGD_TREE_MAX_BINS
+TREE_MAX_CLASSES = 32     # PSGD_TREE_MAX_CLASSES
+TREE_IMPURITIES = {"gini": 0, "entropy": 1}   # PSGD_TREE_GINI / PSGD_TREE_ENTROPY
+
+
+def tree_plan(storage: str, d: int, maxBins: int, K: int, slots: int, total_tiles: int, budget: int = 0) -> dict:
+    """How a level's histogram pass runs a frontier of `slots` slots over rows of d features cut into
+    total_tiles tiles of 256 rows, the 64-bit table of a launch within `budget` bytes (0: 256 MiB)
+    (psgd_tree_plan: host code, no device)."""
+    out = (C.c_int64 * 10)()
+    check(lib().psgd_tree_plan({"f64": 0, "f32": 1}[storage], int(d), int(maxBins), int(K), int(slots), int(total_tiles),
+                               int(budget), out))
+    keys = ("feature_chunk", "slot_subgroup", "replication", "lds_bytes", "groups", "scratch_bytes", "group_slots",
+            "items", "span_rows", "pitch")
+    return {k_: int(v) for k_, v in zip(keys, out)}
 
 
 GMM_MAX_K = 256     # PSGD_GMM_MAX_K
@@ -762,6 +790,55 @@ class Context:
     def kmeans_update_device(self, k: int, d: int, c_ptr, step_ptr, new_ptr, moved_ptr, stream=None):
         """psgd_kmeans_update_device: the next centres [k d] and moved [k] from a step's output."""
         check(self._L.psgd_kmeans_update_device(self.handle, int(k), int(d), c_ptr, step_ptr, new_ptr, moved_ptr, stream))
+
+    # decision tree --------------------------------------------------------------------------------
+    def tree_bin_device(self, thresholds, nbins, max_bins: int, thr_ptr, nb_ptr, bins_ptr, labels_ptr, stream=None):
+        """psgd_tree_bin_device: host thresholds [d, max_bins - 1] / nbins [d] copied to thr_ptr / nb_ptr, the
+        binned rows and label bytes written on `stream`."""
+        check(self._L.psgd_tree_bin_device(self.handle, thresholds.ctypes.data, nbins.ctypes.data, int(max_bins), thr_ptr,
+                                           nb_ptr, bins_ptr, labels_ptr, stream))
+
+    def tree_histogram_device(self, bins_ptr, labels_ptr, slot_ptr, K: int, max_bins: int, slot0: int, n_slots: int,
+                              replication: int, hist_ptr, nbad_ptr, stream=None):
+        """psgd_tree_histogram_device: hist [n_slots, d, max_bins, K] int64 of slots slot0 .. on the device."""
+        check(self._L.psgd_tree_histogram_device(self.handle, bins_ptr, labels_ptr, slot_ptr, int(K), int(max_bins),
+                                                 int(slot0), int(n_slots), int(replication), hist_ptr, nbad_ptr, stream))
+
+    def tree_best_split_device(self, hist_ptr, thr_ptr, nb_ptr, d: int, max_bins: int, K: int, n_slots: int, impurity: int,
+                               min_instances: int, min_info_gain: float, rec_ptr, stream=None):
+        """psgd_tree_best_split_device: rec [n_slots, 6 + 2 K] doubles on the device."""
+        check(self._L.psgd_tree_best_split_device(self.handle, hist_ptr, thr_ptr, nb_ptr, int(d), int(max_bins), int(K),
+                                                  int(n_slots), int(impurity), int(min_instances), float(min_info_gain),
+                                                  rec_ptr, stream))
+
+    def tree_route_device(self, bins_ptr, table_ptr, n_table: int, slot_ptr, stream=None):
+        """psgd_tree_route_device: slot[r] rewritten from table [n_table, 4] int32."""
+        check(self._L.psgd_tree_route_device(self.handle, bins_ptr, table_ptr, int(n_table), slot_ptr, stream))
+
+    @staticmethod
+    def _tree_nodes(nodes):
+        import numpy as np
+        kinds = (("feature", np.int32), ("threshold", np.float64), ("left", np.int32), ("right", np.int32),
+                 ("prediction", np.int32), ("probability", np.float64))
+        return [np.ascontiguousarray(nodes[k], dtype=t) for k, t in kinds]
+
+    def tree_predict(self, nodes, probability: bool = False):
+        """Host-pointer form (psgd_tree_predict): (classes int32 [local rows], probabilities or None) of the
+        tree `nodes` (a mapping of the arrays feature, threshold, left, right, prediction, probability)."""
+        import numpy as np
+        arr = self._tree_nodes(nodes)
+        n = self.local_rows()
+        cls = np.zeros(max(n, 1), dtype=np.int32)
+        prob = np.zeros(max(n, 1), dtype=np.float64) if probability else None
+        check(self._L.psgd_tree_predict(self.handle, len(arr[0]), *[a.ctypes.data for a in arr], cls.ctypes.data,
+                                        None if prob is None else prob.ctypes.data))
+        return cls[:n], None if prob is None else prob[:n]
+
+    def tree_predict_device(self, nodes, cls_ptr, prob_ptr, stream=None):
+        """psgd_tree_predict_device: classes / probabilities (0: none) [local rows] on the device."""
+        arr = self._tree_nodes(nodes)
+        check(self._L.psgd_tree_predict_device(self.handle, len(arr[0]), *[a.ctypes.data for a in arr], cls_ptr,
+                                               prob_ptr or None, stream))
 
     # Gaussian mixture ---------------------------------------------------------------------------
     def gmm_responsibilities(self, A, b, c, mahalanobis: bool = False):

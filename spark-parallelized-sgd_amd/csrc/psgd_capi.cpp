@@ -476,6 +476,8 @@ struct psgd_ctx {
     // Gaussian mixture (psgd_gmm_*): a step's responsibilities, and the host-pointer forms' staging (the
     // scratch is the Gramian's qrec, the tile table the compactions' stab)
     DevBuf mixresp, mixio;
+    // decision tree (psgd_tree_*): a model's node records, and the host-pointer prediction's staging
+    DevBuf tnodes, tio;
 };
 
 namespace {
@@ -849,7 +851,7 @@ int32_t psgd_ctx_destroy(psgd_ctx* ctx) {
                           &ctx->gdescs, &ctx->grows, &ctx->gys, &ctx->gxstate, &ctx->grec, &ctx->gio,
                           &ctx->qrec, &ctx->qio, &ctx->qomega,
                           &ctx->mscratch, &ctx->mio, &ctx->cidx, &ctx->csel, &ctx->stab,
-                          &ctx->kassign, &ctx->kio, &ctx->mixresp, &ctx->mixio, &ctx->watchdog})
+                          &ctx->kassign, &ctx->kio, &ctx->mixresp, &ctx->mixio, &ctx->tnodes, &ctx->tio, &ctx->watchdog})
             b->release();
         for (int k = 0; k < psgd_ctx::kChainEvents; ++k) {
             if (ctx->ev_begin[k]) hipEventDestroy(ctx->ev_begin[k]);
@@ -3471,6 +3473,226 @@ int32_t psgd_kmeans_plan(int32_t layout, int32_t storage, int32_t d, int32_t k, 
     const psgd::KmGeom gm = psgd::kmeans_geometry(layout, storage == PSGD_F32 ? 1 : 0, d, k, total_tiles, 0);
     const int64_t v[PSGD_KMEANS_PLAN_LEN] = {gm.path, gm.cb,      gm.gr,      gm.gc,           gm.span,     gm.n_spans,
                                              gm.n_items, gm.scratch_bytes, gm.lds_bytes, gm.tile_rows, gm.kpad, gm.group};
+    std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
+// ---- Decision-tree classifier (kernels in psgd_tree.hip) ----
+// The binning and the prediction read the rows: the same place in the context as the scoring calls
+// (score_prepare, no epoch state touched). The histogram, split and routing passes read the caller's
+// device buffers alone.
+static int32_t tree_args(int32_t max_bins, int32_t num_classes) {
+    if (max_bins < 2) return fail(PSGD_EINVAL, "max_bins must be at least 2");
+    if (num_classes < 2) return fail(PSGD_EINVAL, "num_classes must be at least 2");
+    if (max_bins > PSGD_TREE_MAX_BINS)
+        return fail(PSGD_EUNSUPPORTED, "a tree with max_bins = " + std::to_string(max_bins) + " exceeds the built maximum of " +
+                                           std::to_string(PSGD_TREE_MAX_BINS) + " (a bin is a byte)");
+    if (num_classes > PSGD_TREE_MAX_CLASSES)
+        return fail(PSGD_EUNSUPPORTED, "a tree over " + std::to_string(num_classes) + " classes exceeds the built maximum of " +
+                                           std::to_string(PSGD_TREE_MAX_CLASSES));
+    return PSGD_OK;
+}
+
+// The registry's rows for a tree pass (ctx->mu held): dense, or PSGD_EUNSUPPORTED.
+static int32_t tree_rows(psgd_ctx* ctx) {
+    if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+    if (ctx->parts.begin()->second.layout == psgd::kCsr)
+        return fail(PSGD_EUNSUPPORTED, "the decision tree needs dense rows (the partitions are CSR)");
+    return PSGD_OK;
+}
+
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+int32_t psgd_tree_bin_device(psgd_ctx* ctx, const double* thresholds, const int32_t* nbins, int32_t max_bins,
+                             double* d_thresholds, int32_t* d_nbins, uint8_t* d_bins, uint8_t* d_labels, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!thresholds || !nbins || !d_thresholds || !d_nbins || !d_bins || !d_labels)
+        return fail(PSGD_EINVAL, "thresholds/nbins/d_thresholds/d_nbins/d_bins/d_labels are null");
+    int32_t rc = tree_args(max_bins, 2);
+    if (rc) return rc;
+    if (!aligned16(d_bins)) return fail(PSGD_EINVAL, "d_bins must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = tree_rows(ctx);
+    if (rc) return rc;
+    const Part& first = ctx->parts.begin()->second;
+    const int32_t d = first.d, tp = max_bins - 1;
+    for (int32_t f = 0; f < d; ++f) {
+        if (nbins[f] < 1 || nbins[f] > max_bins)
+            return fail(PSGD_EINVAL, "feature " + std::to_string(f) + " has " + std::to_string(nbins[f]) +
+                                         " bins: 1 .. max_bins are allowed");
+        for (int32_t j = 0; j + 1 < nbins[f]; ++j) {
+            const double t = thresholds[(size_t)f * tp + j];
+            if (!(t == t) || (j > 0 && !(t > thresholds[(size_t)f * tp + j - 1])))
+                return fail(PSGD_EINVAL, "the thresholds of feature " + std::to_string(f) + " are not strictly ascending");
+        }
+    }
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    HIP_TRY(hipMemcpyAsync(d_thresholds, thresholds, (size_t)d * tp * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_nbins, nbins, (size_t)d * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    // the caller's arrays are pageable in general: the copies have left them when this returns
+    HIP_TRY(hipStreamSynchronize(st));
+    const int P = (int)ctx->parts.size();
+    const int e = psgd::launch_tree_bin(ctx->descs.as<psgd::ChainDesc>(), ctx->cidx.as<int64_t>() + P, P, ctx->row_off.back(),
+                                        first.dtype == PSGD_F32 ? 1 : 0, d, max_bins, d_thresholds, d_nbins, d_bins,
+                                        d_labels, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree binning launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_histogram_device(psgd_ctx* ctx, const uint8_t* d_bins, const uint8_t* d_labels, const int32_t* d_slot,
+                                   int32_t num_classes, int32_t max_bins, int32_t slot0, int32_t n_slots,
+                                   int32_t replication, int64_t* d_hist, int64_t* d_nbad, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_bins || !d_labels || !d_slot || !d_hist || !d_nbad)
+        return fail(PSGD_EINVAL, "d_bins/d_labels/d_slot/d_hist/d_nbad are null");
+    int32_t rc = tree_args(max_bins, num_classes);
+    if (rc) return rc;
+    if (slot0 < 0 || n_slots < 1) return fail(PSGD_EINVAL, "slot0 must be >= 0 and n_slots >= 1");
+    if (replication < 0 || replication > 2) return fail(PSGD_EINVAL, "replication must be 0 (the plan's), 1 or 2");
+    if (!aligned16(d_bins)) return fail(PSGD_EINVAL, "d_bins must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);   // (the row count is the registry's)
+    if (rc) return rc;
+    const int64_t n_rows = ctx->row_off.back();
+    const psgd::TreeGeom gm = psgd::tree_geometry(ctx->parts.begin()->second.d, max_bins, num_classes, n_slots,
+                                                  (n_rows + psgd::kTreeTileRows - 1) / psgd::kTreeTileRows, INT64_MAX,
+                                                  replication);
+    const int e = psgd::launch_tree_hist(d_bins, d_labels, d_slot, n_rows, gm, slot0, n_slots, d_hist, d_nbad, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree histogram launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_best_split_device(psgd_ctx* ctx, const int64_t* d_hist, const double* d_thresholds, const int32_t* d_nbins,
+                                    int32_t d, int32_t max_bins, int32_t num_classes, int32_t n_slots, int32_t impurity,
+                                    int64_t min_instances, double min_info_gain, double* d_rec, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_hist || !d_thresholds || !d_nbins || !d_rec) return fail(PSGD_EINVAL, "d_hist/d_thresholds/d_nbins/d_rec are null");
+    const int32_t rc = tree_args(max_bins, num_classes);
+    if (rc) return rc;
+    if (d < 1 || n_slots < 1) return fail(PSGD_EINVAL, "d and n_slots must be positive");
+    if (impurity != PSGD_TREE_GINI && impurity != PSGD_TREE_ENTROPY)
+        return fail(PSGD_EINVAL, "unknown impurity " + std::to_string(impurity));
+    if (min_instances < 1 || !(min_info_gain >= 0.0))
+        return fail(PSGD_EINVAL, "min_instances must be >= 1 and min_info_gain >= 0");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int e = psgd::launch_tree_best_split(d_hist, d_thresholds, d_nbins, d, max_bins, num_classes, n_slots, impurity,
+                                               (double)min_instances, min_info_gain, d_rec, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree split launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_route_device(psgd_ctx* ctx, const uint8_t* d_bins, const int32_t* d_table, int32_t n_table, int32_t* d_slot,
+                               void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_bins || !d_table || !d_slot) return fail(PSGD_EINVAL, "d_bins/d_table/d_slot are null");
+    if (n_table < 1) return fail(PSGD_EINVAL, "n_table must be positive");
+    if (!aligned16(d_table)) return fail(PSGD_EINVAL, "d_table must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int32_t rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    const int32_t d = ctx->parts.begin()->second.d;
+    const int e = psgd::launch_tree_route(d_bins, 16 * ((d + 15) / 16), ctx->row_off.back(), d_table, n_table, d_slot,
+                                          ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree routing launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+namespace {
+struct TreeNodeRec {   // psgd_tree.hip's TreeNode
+    double threshold, prob;
+    int32_t feature, left, right, pred;
+};
+}  // namespace
+
+int32_t psgd_tree_predict_device(psgd_ctx* ctx, int32_t n_nodes, const int32_t* feature, const double* threshold,
+                                 const int32_t* left, const int32_t* right, const int32_t* prediction,
+                                 const double* probability, int32_t* d_classes, double* d_prob, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!feature || !threshold || !left || !right || !prediction || !probability || !d_classes)
+        return fail(PSGD_EINVAL, "a node array or d_classes is null");
+    if (n_nodes < 1) return fail(PSGD_EINVAL, "n_nodes must be positive");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int32_t rc = tree_rows(ctx);
+    if (rc) return rc;
+    const Part& first = ctx->parts.begin()->second;
+    std::vector<TreeNodeRec> nodes((size_t)n_nodes);
+    for (int32_t i = 0; i < n_nodes; ++i) {
+        const bool leaf = feature[i] < 0;
+        // a child lies after its parent, so every walk ends; a feature is a column of the rows
+        if (!leaf && (feature[i] >= first.d || left[i] <= i || left[i] >= n_nodes || right[i] <= i || right[i] >= n_nodes))
+            return fail(PSGD_EINVAL, "node " + std::to_string(i) + " has a feature past the rows' or a child that is not a later node");
+        nodes[(size_t)i] = TreeNodeRec{threshold[i], probability[i], leaf ? -1 : feature[i], left[i], right[i], prediction[i]};
+    }
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    HIP_TRY(ctx->tnodes.ensure(nodes.size() * sizeof(TreeNodeRec)));
+    HIP_TRY(hipMemcpyAsync(ctx->tnodes.p, nodes.data(), nodes.size() * sizeof(TreeNodeRec), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the records leave a host vector of this call
+    const int P = (int)ctx->parts.size();
+    const int e = psgd::launch_tree_predict(ctx->descs.as<psgd::ChainDesc>(), ctx->cidx.as<int64_t>() + P, P,
+                                            ctx->row_off.back(), first.dtype == PSGD_F32 ? 1 : 0, ctx->tnodes.p, n_nodes,
+                                            d_classes, d_prob, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree prediction launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_predict(psgd_ctx* ctx, int32_t n_nodes, const int32_t* feature, const double* threshold, const int32_t* left,
+                          const int32_t* right, const int32_t* prediction, const double* probability, int32_t* classes,
+                          double* prob) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!classes) return fail(PSGD_EINVAL, "classes is null");
+    size_t n = 0;
+    int32_t* d_cls = nullptr;
+    double* d_prob = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        for (auto& kv : ctx->parts) n += (size_t)kv.second.n_rows;
+        DeviceGuard g(ctx->device);
+        const int32_t rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        const size_t m = std::max<size_t>(n, 1);
+        HIP_TRY(ctx->tio.ensure(m * (sizeof(double) + sizeof(int32_t))));
+        d_prob = ctx->tio.as<double>();
+        d_cls = reinterpret_cast<int32_t*>(d_prob + m);
+    }
+    const int32_t rc = psgd_tree_predict_device(ctx, n_nodes, feature, threshold, left, right, prediction, probability, d_cls,
+                                                prob ? d_prob : nullptr, ctx->stream);
+    if (rc || n == 0) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(classes, d_cls, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (prob) HIP_TRY(hipMemcpyAsync(prob, d_prob, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_plan(int32_t storage, int32_t d, int32_t max_bins, int32_t num_classes, int32_t slots, int64_t total_tiles,
+                       int64_t budget, int64_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
+    if (d <= 0 || slots < 1 || total_tiles < 0) return fail(PSGD_EINVAL, "d and slots must be positive, total_tiles >= 0");
+    const int32_t rc = tree_args(max_bins, num_classes);
+    if (rc) return rc;
+    if (budget <= 0) budget = PSGD_TREE_SCRATCH_BUDGET;
+    const psgd::TreeGeom gm = psgd::tree_geometry(d, max_bins, num_classes, slots, total_tiles, budget, 0);
+    const int64_t v[PSGD_TREE_PLAN_LEN] = {gm.fchunk,   gm.sgroup,  gm.repl,      gm.lds_bytes, gm.n_groups, gm.scratch_bytes,
+                                           gm.group_slots, gm.n_items, gm.span_rows, gm.pitch};
     std::memcpy(out, v, sizeof v);
     return PSGD_OK;
 }

@@ -534,6 +534,47 @@ int launch_gmm_step(const ChainDesc* descs, const KmPart* tab, int n_parts, int6
                     const GmmGeom& gm, int storage, const double* A, const double* b, const double* c, double* scratch,
                     double* resp, double* out, int num_cus, hipStream_t st);
 
+// ---- Decision-tree classifier (psgd_tree.hip: psgd_tree_*) ----
+// The plan of a level's histogram pass: host code, no device (psgd_tree_plan reports it). Dense rows only.
+constexpr int kTreeMaxBins = 256;
+constexpr int kTreeMaxClasses = 32;
+constexpr int kTreeLdsCells = 16384;     // uint32 counters a workgroup of tree_hist keeps: 64 KiB, two workgroups a CU
+constexpr int kTreeTileRows = 256;       // rows a tile of the local row order
+struct TreeGeom {
+    int32_t d, bins, classes;
+    int32_t pitch;                 // bytes of a binned row: d rounded up to 16
+    int32_t fchunk;                // features an item counts: whole vectors of 16, or 1, 2, 4, 8 of one vector
+    int32_t sgroup;                // slots an item counts
+    int32_t repl;                  // copies of the sub-table in LDS: 1, or 2 by row parity
+    int32_t n_fchunks, n_sgroups;  // feature chunks of a row, slot sub-groups of a group
+    int32_t group_slots, n_groups; // slots whose 64-bit table fits the budget, launches a level
+    int64_t span_rows, n_spans;    // rows a span (whole tiles), spans
+    int64_t n_items;               // spans x feature chunks x sub-groups
+    int64_t lds_bytes;             // dynamic LDS of the launch
+    int64_t scratch_bytes;         // the 64-bit table of a group
+};
+// repl: 0 the plan's choice, 1 or 2 to force it (2 halves the cells a copy may take).
+TreeGeom tree_geometry(int d, int bins, int classes, int slots, int64_t n_tiles, int64_t budget, int repl);
+// bins [n_rows][pitch] and labels [n_rows] bytes in local row order (row_off [n_parts + 1]) from thresholds
+// thr [d][bins - 1] and nbins [d] on the device.
+int launch_tree_bin(const ChainDesc* descs, const int64_t* row_off, int n_parts, int64_t n_rows, int storage, int d,
+                    int bins, const double* thr, const int32_t* nbins, uint8_t* out, uint8_t* labels, int num_cus,
+                    hipStream_t st);
+// hist [n_slots][d][bins][classes] (zeroed here) of the rows whose slot lies in [slot0, slot0 + n_slots);
+// *nbad += the rows among them whose label byte is >= classes.
+int launch_tree_hist(const uint8_t* bins, const uint8_t* labels, const int32_t* slot, int64_t n_rows, const TreeGeom& gm,
+                     int slot0, int n_slots, int64_t* hist, int64_t* nbad, hipStream_t st);
+// rec [n_slots][6 + 2 classes] = {feature (-1: a leaf), bin, threshold, gain, impurity, n, tot, L}.
+int launch_tree_best_split(const int64_t* hist, const double* thr, const int32_t* nbins, int d, int bins, int classes,
+                           int n_slots, int impurity, double min_inst, double min_gain, double* rec, hipStream_t st);
+// slot[r] <- table[slot[r]]'s left or right slot ({feature, bin, left, right}; feature < 0 or a slot past the table: -1).
+int launch_tree_route(const uint8_t* bins, int pitch, int64_t n_rows, const int32_t* table, int n_table, int32_t* slot,
+                      int num_cus, hipStream_t st);
+// cls [n_rows] / prob [n_rows] (nullable) in local row order; nodes: n_nodes records of 32 bytes {threshold,
+// probability, feature (-1: a leaf), left, right, prediction}, checked by the caller.
+int launch_tree_predict(const ChainDesc* descs, const int64_t* row_off, int n_parts, int64_t n_rows, int storage,
+                        const void* nodes, int n_nodes, int32_t* cls, double* prob, int num_cus, hipStream_t st);
+
 // w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
 // the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
 int64_t gd_update_blocks(int d);

@@ -901,6 +901,138 @@ class HipEngine(ShardedEngine):
         self.stream.synchronize()
         return new, moved
 
+    # decision tree (psgd_tree_*_device; tree.py) ---------------------------------------------------
+    def _tree_run(self, call, rows: bool = True):
+        """call() enqueued on self.stream after the caller's stream, the registry current when the pass
+        reads it (`rows`); the caller's stream then waits for it."""
+        torch = self.torch
+        caller = torch.cuda.current_stream(self.dev)
+        self.stream.wait_stream(caller)
+        with torch.cuda.stream(self.stream):
+            if rows and self.n_local > 0:
+                with self.ctx.engine_lock:
+                    if self.ctx.registered_token != self._key:
+                        self._register(self._data)
+                    out = call(True)
+            else:
+                out = call(not rows)
+        caller.wait_stream(self.stream)
+        for t in (out if isinstance(out, tuple) else (out,)):
+            if torch.is_tensor(t):
+                t.record_stream(caller)
+        return out
+
+    def tree_bin(self, thresholds, nbins):
+        """The binned copy of this rank's rows (psgd_tree_bin_device; include/psgd.h has the definitions): a
+        tree.TreeBins of device tensors -- bins uint8 [local_rows(), pitch] with pitch = num_features rounded
+        up to 16, the label bytes, and the thresholds [d, maxBins - 1] / nbins [d] the later passes read.
+        thresholds: a host array [d, maxBins - 1], row f ascending over its first nbins[f] - 1 entries."""
+        from .tree import TreeBins
+        torch = self.torch
+        nf, n = self._data.num_features, self.local_rows()
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+        nb = np.ascontiguousarray(nbins, dtype=np.int32)
+        if thr.ndim != 2 or thr.shape[0] != nf or nb.shape != (nf,):
+            raise IllegalArgumentException(
+                f"requirement failed: the thresholds must be [{nf}, maxBins - 1] and nbins [{nf}] (got {thr.shape}, {nb.shape})")
+        B, pitch = thr.shape[1] + 1, 16 * ((nf + 15) // 16)
+        if self._data.partitions and isinstance(self._data.partitions[0], (CsrPartition, DeviceCsrPartition)):
+            raise N.UnsupportedOperationException("the decision tree needs dense rows (the partitions are CSR)")
+
+        def call(run):
+            bins = torch.zeros((max(n, 1), pitch), dtype=torch.uint8, device=self.dev)
+            labels = torch.zeros(max(n, 1), dtype=torch.uint8, device=self.dev)
+            d_thr = torch.from_numpy(thr.copy()).to(self.dev)
+            d_nb = torch.from_numpy(nb.copy()).to(self.dev)
+            if run:
+                self.ctx.tree_bin_device(thr, nb, B, d_thr.data_ptr(), d_nb.data_ptr(), bins.data_ptr(), labels.data_ptr(),
+                                         self.stream.cuda_stream)
+            return TreeBins(bins[:n], labels[:n], d_thr, d_nb, B)
+        return self._tree_run(call)
+
+    def tree_slots(self):
+        """slot[r] of this rank's rows before the first level: zeros (int32, on the device)."""
+        with self.torch.cuda.stream(self.stream):
+            t = self.torch.zeros(max(self.local_rows(), 1), dtype=self.torch.int32, device=self.dev)
+        self.stream.synchronize()
+        return t[: self.local_rows()]
+
+    def tree_histogram(self, bins, slots, K: int, group=None, replication: int = 0):
+        """H[slot][f][b][c] of the slots `group` = (first slot, slots) -- default (0, 1), the root -- over every
+        row of the data, on all ranks: a device int64 tensor [slots, d, maxBins, K]
+        (psgd_tree_histogram_device). The ranks add their tables with an integer all-reduce: exact in any
+        order. A label that is not a whole number in [0, K) raises, as confusion() does."""
+        torch = self.torch
+        slot0, n_slots = (0, 1) if group is None else (int(group[0]), int(group[1]))
+        nf, B = self._data.num_features, bins.max_bins
+
+        def call(run):
+            buf = torch.zeros(1 + n_slots * nf * B * K, dtype=torch.int64, device=self.dev)   # {n_bad, H}
+            if run:
+                self.ctx.tree_histogram_device(bins.bins.data_ptr(), bins.labels.data_ptr(), slots.data_ptr(), K, B, slot0,
+                                               n_slots, replication, buf.data_ptr() + 8, buf.data_ptr(),
+                                               self.stream.cuda_stream)
+            if self.world > 1:
+                import torch.distributed as dist
+                if dist.get_backend() == "gloo":   # (through the host: gloo takes CPU tensors)
+                    h = buf.cpu()
+                    dist.all_reduce(h)
+                    buf = h.to(self.dev)
+                else:
+                    dist.all_reduce(buf)
+            return buf
+        buf = self._tree_run(call)
+        bad = int(buf[:1].cpu().numpy()[0])
+        if bad > 0:
+            raise IllegalArgumentException(f"requirement failed: {bad} labels are not whole numbers in [0, {K})")
+        return buf[1:].view(n_slots, nf, B, K)
+
+    def tree_best_split(self, hist, bins, impurity: str = "gini", minInstancesPerNode: int = 1, minInfoGain: float = 0.0):
+        """One record a slot of `hist` [slots, d, maxBins, K] (psgd_tree_best_split_device): a device tensor
+        [slots, 6 + 2 K] of doubles {feature (-1: a leaf), bin, threshold, gain, impurity, n, tot[K], L[K]}."""
+        torch = self.torch
+        n_slots, nf, B, K = (int(v) for v in hist.shape)
+
+        def call(_run):
+            rec = torch.zeros((n_slots, 6 + 2 * K), dtype=torch.float64, device=self.dev)
+            self.ctx.tree_best_split_device(hist.data_ptr(), bins.thresholds.data_ptr(), bins.nbins.data_ptr(), nf, B, K,
+                                            n_slots, N.TREE_IMPURITIES[impurity], minInstancesPerNode, minInfoGain,
+                                            rec.data_ptr(), self.stream.cuda_stream)
+            return rec
+        return self._tree_run(call, rows=False)
+
+    def tree_route(self, bins, slots, table):
+        """slots[r] <- the child's slot from `table` [slots of the frontier, 4] int32 {feature, bin, left slot,
+        right slot} (a host array; feature -1: the slot is a leaf), in place (psgd_tree_route_device)."""
+        torch = self.torch
+        tab = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, 4)
+
+        def call(run):
+            d_tab = torch.from_numpy(tab.copy()).to(self.dev)
+            if run and slots.numel() > 0:
+                self.ctx.tree_route_device(bins.bins.data_ptr(), d_tab.data_ptr(), tab.shape[0], slots.data_ptr(),
+                                           self.stream.cuda_stream)
+            self.stream.synchronize()   # d_tab is a temporary of this call
+            return slots
+        return self._tree_run(call)
+
+    def tree_predict(self, nodes, probability: bool = False):
+        """(classes, probabilities) of every row of this rank's partitions under the tree `nodes` (a mapping of
+        the arrays feature, threshold, left, right, prediction, probability; node 0 the root): device tensors
+        of local_rows() int32 / doubles in partition and iterator order (psgd_tree_predict_device;
+        probabilities is None unless asked for)."""
+        torch = self.torch
+        n = self.local_rows()
+
+        def call(run):
+            cls = torch.zeros(max(n, 1), dtype=torch.int32, device=self.dev)
+            prob = torch.zeros(max(n, 1), dtype=torch.float64, device=self.dev) if probability else None
+            if run:
+                self.ctx.tree_predict_device(nodes, cls.data_ptr(), 0 if prob is None else prob.data_ptr(),
+                                             self.stream.cuda_stream)
+            return cls[:n], None if prob is None else prob[:n]
+        return self._tree_run(call)
+
     # Gaussian mixture (psgd_gmm_*_device; clustering.py) -------------------------------------------
     def _gmm_operands(self, weights, gaussians):
         """(k, [A | b | c] as one f64 device tensor) of a mixture of stat.MultivariateGaussian components
