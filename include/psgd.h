@@ -736,6 +736,82 @@ int32_t psgd_tree_predict_device(psgd_ctx* ctx, int32_t n_nodes, const int32_t* 
 int32_t psgd_tree_plan(int32_t storage, int32_t d, int32_t max_bins, int32_t num_classes, int32_t slots, int64_t total_tiles,
                        int64_t budget, int64_t* out);
 
+/* A random-forest classifier over the tree's binned rows -- the passes behind RandomForest.trainClassifier,
+ * a group of G trees trained together, level by level. The project's restatement of MLlib 1.6.1's model, not
+ * pinned to its source. All counts are exact integers: every output has the same bits from call to call and
+ * however the rows are spread over ranks.
+ * Bag weight of (seed, tree t, global row g): g is the row's index in the whole data set in partition order
+ *   (row0 + the local row). mix(x), in uint64 arithmetic: x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *   x *= 0x94D049BB133111EB; x ^= x >> 31. GOLD = 0x9E3779B97F4A7C15; key_t = mix(seed + (t + 1) GOLD);
+ *   u = mix(key_t + (g + 1) GOLD) >> 11, a 53-bit integer. The caller passes 15 ascending thresholds cut[0..14]
+ *   (host memory); the weight is the number of k with u >= cut[k]: 0 .. 15, integer compares only. The host
+ *   builds cut[k] = ceil(F(k) 2^53) from the cumulative distribution it wants (Poisson, Bernoulli, all ones).
+ *   The passes recompute the weight where they need it; nothing of trees x rows is stored for it.
+ *   psgd_forest_bag_device writes the weights of trees tree0 .. tree0 + n_trees - 1 as bytes [n_trees][rows].
+ * Frontier: the open nodes of the group's trees, numbered a in [0, A) tree by tree: node_tree[A] (int32,
+ *   ascending: the node's tree within the group), tree_base[G + 1] (tree t's nodes are tree_base[t] ..
+ *   tree_base[t + 1] - 1), sub[A][m] (int32: the node's feature subset, ascending, each in [0, d)), and
+ *   slot[G][rows] (int32: the row's index within tree t's own nodes, -1 once the row is finished in tree t).
+ * Histogram: H[a - node0][j][b][c] (64-bit, compact: m positions a node) = the sum of the bag weights of the
+ *   local rows with tree_base[t] + slot[t][r] = a, bins[r][sub[a][j]] = b and label c, for the nodes node0 ..
+ *   node0 + n_nodes - 1 of the frontier; the call zeroes the table first. tree0 is the forest's index of the
+ *   group's tree 0. Every local row whose label byte is >= num_classes adds 1 to *d_nbad (the caller zeroes
+ *   it) once a call, whatever its slots and weights, and to no cell.
+ * Best split of a node: psgd_tree_best_split_device's rules over the node's m positions on the weighted
+ *   counts (min_instances compares weighted counts). Ties go to the lowest position, which is the lowest
+ *   feature, then the lowest bin. The record layout is the tree's; its feature field is the real feature
+ *   sub[a][j]. d_sub points at the first node of d_hist.
+ * Routing: d_table[a] = {feature, bin, left, right} (int32 x 4) over the whole frontier. slot[t][r] >= 0
+ *   becomes the left child's when bins[r][feature] <= bin, else the right child's: indices within tree t's
+ *   next frontier, -1 for a finished leaf. A node with feature < 0 or a slot past the tree's nodes gives -1.
+ * Prediction: the trees' node arrays concatenated, tree t at tree_off[t] .. tree_off[t + 1] - 1 (tree_off[0]
+ *   = 0), left and right as indices within the tree, a node's children after it. Every tree votes its
+ *   leaf's prediction; the class of most votes wins, ties to the lowest class. d_votes / votes (nullable)
+ *   receive the [rows][num_classes] int32 vote table.
+ * Errors: those of the tree calls (null pointers, d_bins or d_table off a 16-byte boundary, num_classes < 2
+ *   or > PSGD_TREE_MAX_CLASSES, max_bins > PSGD_TREE_MAX_BINS, CSR partitions, no partition registered), and
+ *   PSGD_EINVAL for a cut that does not ascend, negative row0 or tree0, m outside [1, d], nodes outside the
+ *   frontier, a tree without nodes or a leaf that predicts a class outside [0, num_classes). */
+#define PSGD_FOREST_SLOT_BUDGET (1ll << 30)
+int32_t psgd_forest_bag_device(psgd_ctx* ctx, uint64_t seed, const uint64_t* cut, int64_t row0, int32_t tree0, int32_t n_trees,
+                               uint8_t* d_weights, void* stream);
+int32_t psgd_forest_histogram_device(psgd_ctx* ctx, const uint8_t* d_bins, const uint8_t* d_labels, const int32_t* d_slot,
+                                     int32_t n_trees, const int32_t* d_node_tree, const int32_t* d_tree_base,
+                                     const int32_t* d_sub, int32_t n_frontier, int32_t m, int32_t num_classes, int32_t max_bins,
+                                     int32_t node0, int32_t n_nodes, uint64_t seed, const uint64_t* cut, int64_t row0,
+                                     int32_t tree0, int64_t* d_hist, int64_t* d_nbad, void* stream);
+int32_t psgd_forest_best_split_device(psgd_ctx* ctx, const int64_t* d_hist, const double* d_thresholds, const int32_t* d_nbins,
+                                      const int32_t* d_sub, int32_t m, int32_t max_bins, int32_t num_classes, int32_t n_nodes,
+                                      int32_t impurity, int64_t min_instances, double min_info_gain, double* d_rec,
+                                      void* stream);
+int32_t psgd_forest_route_device(psgd_ctx* ctx, const uint8_t* d_bins, const int32_t* d_table, const int32_t* d_tree_base,
+                                 int32_t n_trees, int32_t* d_slot, void* stream);
+int32_t psgd_forest_predict(psgd_ctx* ctx, int32_t n_trees, const int32_t* tree_off, const int32_t* feature,
+                            const double* threshold, const int32_t* left, const int32_t* right, const int32_t* prediction,
+                            int32_t num_classes, int32_t* classes, int32_t* votes);
+int32_t psgd_forest_predict_device(psgd_ctx* ctx, int32_t n_trees, const int32_t* tree_off, const int32_t* feature,
+                                   const double* threshold, const int32_t* left, const int32_t* right,
+                                   const int32_t* prediction, int32_t num_classes, int32_t* d_classes, int32_t* d_votes,
+                                   void* stream);
+
+/* How psgd_forest_histogram_device runs a frontier of `nodes` nodes with m subset features each over rows of
+ * d features cut into total_tiles tiles of 256 local rows, and how many of n_trees trees train together over
+ * n_rows local rows: host code, no device and no context. scratch_budget: the bytes the 64-bit table of one
+ * launch may take (<= 0: PSGD_TREE_SCRATCH_BUDGET); slot_budget: the bytes slot[G][n_rows] may take (<= 0:
+ * PSGD_FOREST_SLOT_BUDGET). out[PSGD_FOREST_PLAN_LEN] receives
+ *   [0] J, the subset positions a work item counts (m, or fewer when m max_bins num_classes cells exceed LDS);
+ *   [1] S, the nodes of a sub-group;
+ *   [2] bytes of dynamic LDS of the launch: the table [S][J][max_bins][num_classes] uint32, the subsets
+ *       [S][J], the entry list (8 KiB) and the row tile (pitch + 16 bytes a row); 156 KiB at most;
+ *   [3] the node groups of a level; [4] bytes of the 64-bit table of a group; [5] the nodes of a group;
+ *   [6] the work items of a launch (spans x subset chunks x sub-groups); [7] the rows of a span;
+ *   [8] the trees of a tree group; [9] the rows of the LDS row tile; [10] the pitch of a binned row.
+ * Errors: PSGD_EINVAL for a null out, d <= 0, m outside [1, d], nodes < 1, n_trees < 1, negative total_tiles
+ * or n_rows, max_bins < 2 or num_classes < 2; PSGD_EUNSUPPORTED past the tree's maxima. */
+#define PSGD_FOREST_PLAN_LEN 11
+int32_t psgd_forest_plan(int32_t d, int32_t max_bins, int32_t num_classes, int32_t m, int32_t nodes, int32_t n_trees,
+                         int64_t total_tiles, int64_t n_rows, int64_t scratch_budget, int64_t slot_budget, int64_t* out);
+
 /* One EM step of a Gaussian mixture over every registered row -- the passes behind MLlib 1.6.1's
  * GaussianMixture and GaussianMixtureModel.predictSoft. Dense rows only. A model is k components
  * (w_j, mu_j, Sigma_j), 1 <= k <= PSGD_GMM_MAX_K, over d <= PSGD_GMM_MAX_D features. The host prepares,

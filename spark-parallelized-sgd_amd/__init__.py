@@ -21,7 +21,8 @@ from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradi
 from .newton import HessianSum, Newton, hessian_sum, runNewton
 from .clustering import (GaussianMixture, GaussianMixtureModel, GaussianMixtureStep, KMeans, KMeansModel, KMeansStep,
                          gmm_step, kmeans_step)
-from .tree import DecisionTree, DecisionTreeModel, TreeBins, find_splits
+from .tree import (DecisionTree, DecisionTreeModel, ForestFrontier, RandomForest, RandomForestModel, TreeBins, find_splits,
+                   forest_cut, forest_subset, forest_subset_size)
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
@@ -39,6 +40,7 @@ __all__ = [
     "KMeans", "KMeansModel", "KMeansStep", "kmeans_step",
     "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureStep", "gmm_step", "MultivariateGaussian",
     "DecisionTree", "DecisionTreeModel", "TreeBins", "find_splits",
+    "RandomForest", "RandomForestModel", "ForestFrontier", "forest_cut", "forest_subset", "forest_subset_size",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
     "QRFactor", "QRDecomposition", "qr_factor", "least_squares", "tallSkinnyQR",
     "multiply", "computePrincipalComponents", "computeSVD", "PCA", "PCAModel",

@@ -44,6 +44,8 @@ EXPORTED = (
     "psgd_kmeans_update_device", "psgd_kmeans_plan",
     "psgd_tree_bin_device", "psgd_tree_histogram_device", "psgd_tree_best_split_device", "psgd_tree_route_device",
     "psgd_tree_predict", "psgd_tree_predict_device", "psgd_tree_plan",
+    "psgd_forest_bag_device", "psgd_forest_histogram_device", "psgd_forest_best_split_device", "psgd_forest_route_device",
+    "psgd_forest_predict", "psgd_forest_predict_device", "psgd_forest_plan",
     "psgd_gmm_responsibilities", "psgd_gmm_responsibilities_device", "psgd_gmm_moments_device",
     "psgd_gmm_step", "psgd_gmm_step_device", "psgd_gmm_plan",
     "psgd_binary_counts", "psgd_binary_counts_device", "psgd_binary_counts_model", "psgd_binary_counts_model_device",
@@ -191,6 +193,17 @@ def lib():
             "psgd_tree_predict": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_tree_predict_device": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_tree_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, vp], C.c_int32),
+            "psgd_forest_bag_device": ([vp, C.c_uint64, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp], C.c_int32),
+            "psgd_forest_histogram_device": ([vp, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int32, vp, vp,
+                                              vp], C.c_int32),
+            "psgd_forest_best_split_device": ([vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int64, C.c_double, vp, vp], C.c_int32),
+            "psgd_forest_route_device": ([vp, vp, vp, vp, C.c_int32, vp, vp], C.c_int32),
+            "psgd_forest_predict": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp], C.c_int32),
+            "psgd_forest_predict_device": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp, vp], C.c_int32),
+            "psgd_forest_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64,
+                                  C.c_int64, C.c_int64, vp], C.c_int32),
             "psgd_gmm_responsibilities": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_gmm_responsibilities_device": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_gmm_moments_device": ([vp, C.c_int32, vp, vp, vp], C.c_int32),
@@ -358,6 +371,18 @@ def tree_plan(storage: str, d: int, maxBins: int, K: int, slots: int, total_tile
                                int(budget), out))
     keys = ("feature_chunk", "slot_subgroup", "replication", "lds_bytes", "groups", "scratch_bytes", "group_slots",
             "items", "span_rows", "pitch")
+    return {k_: int(v) for k_, v in zip(keys, out)}
+
+
+def forest_plan(d: int, maxBins: int, K: int, m: int, nodes: int, numTrees: int, total_tiles: int, n_rows: int,
+                scratchBudget: int = 0, slotBudget: int = 0) -> dict:
+    """How a level's forest histogram pass runs a frontier of `nodes` nodes with m subset features each, and how
+    many of numTrees trees train together over n_rows local rows (psgd_forest_plan: host code, no device)."""
+    out = (C.c_int64 * 11)()
+    check(lib().psgd_forest_plan(int(d), int(maxBins), int(K), int(m), int(nodes), int(numTrees), int(total_tiles),
+                                 int(n_rows), int(scratchBudget), int(slotBudget), out))
+    keys = ("subset_chunk", "node_subgroup", "lds_bytes", "groups", "scratch_bytes", "group_nodes", "items", "span_rows",
+            "group_trees", "tile_rows", "pitch")
     return {k_: int(v) for k_, v in zip(keys, out)}
 
 
@@ -839,6 +864,58 @@ class Context:
         arr = self._tree_nodes(nodes)
         check(self._L.psgd_tree_predict_device(self.handle, len(arr[0]), *[a.ctypes.data for a in arr], cls_ptr,
                                                prob_ptr or None, stream))
+
+    # random forest --------------------------------------------------------------------------------
+    def forest_bag_device(self, seed: int, cut, row0: int, tree0: int, n_trees: int, w_ptr, stream=None):
+        """psgd_forest_bag_device: the bag weights [n_trees, local rows] uint8 of trees tree0 .. (cut: 15 uint64)."""
+        check(self._L.psgd_forest_bag_device(self.handle, int(seed), cut.ctypes.data, int(row0), int(tree0), int(n_trees),
+                                             w_ptr, stream))
+
+    def forest_histogram_device(self, bins_ptr, labels_ptr, slot_ptr, n_trees: int, node_tree_ptr, tree_base_ptr, sub_ptr,
+                                n_frontier: int, m: int, K: int, max_bins: int, node0: int, n_nodes: int, seed: int, cut,
+                                row0: int, tree0: int, hist_ptr, nbad_ptr, stream=None):
+        """psgd_forest_histogram_device: hist [n_nodes, m, max_bins, K] int64 of frontier nodes node0 .. ."""
+        check(self._L.psgd_forest_histogram_device(self.handle, bins_ptr, labels_ptr, slot_ptr, int(n_trees), node_tree_ptr,
+                                                   tree_base_ptr, sub_ptr, int(n_frontier), int(m), int(K), int(max_bins),
+                                                   int(node0), int(n_nodes), int(seed), cut.ctypes.data, int(row0),
+                                                   int(tree0), hist_ptr, nbad_ptr, stream))
+
+    def forest_best_split_device(self, hist_ptr, thr_ptr, nb_ptr, sub_ptr, m: int, max_bins: int, K: int, n_nodes: int,
+                                 impurity: int, min_instances: int, min_info_gain: float, rec_ptr, stream=None):
+        """psgd_forest_best_split_device: rec [n_nodes, 6 + 2 K] doubles on the device."""
+        check(self._L.psgd_forest_best_split_device(self.handle, hist_ptr, thr_ptr, nb_ptr, sub_ptr, int(m), int(max_bins),
+                                                    int(K), int(n_nodes), int(impurity), int(min_instances),
+                                                    float(min_info_gain), rec_ptr, stream))
+
+    def forest_route_device(self, bins_ptr, table_ptr, tree_base_ptr, n_trees: int, slot_ptr, stream=None):
+        """psgd_forest_route_device: slot[t][r] rewritten from table [A, 4] int32."""
+        check(self._L.psgd_forest_route_device(self.handle, bins_ptr, table_ptr, tree_base_ptr, int(n_trees), slot_ptr, stream))
+
+    @staticmethod
+    def _forest_nodes(trees):
+        """(tree_off [T + 1], the concatenated feature, threshold, left, right, prediction arrays) of node mappings."""
+        import numpy as np
+        off = np.concatenate([[0], np.cumsum([len(t["feature"]) for t in trees])]).astype(np.int32)
+        kinds = (("feature", np.int32), ("threshold", np.float64), ("left", np.int32), ("right", np.int32),
+                 ("prediction", np.int32))
+        return [off] + [np.ascontiguousarray(np.concatenate([np.asarray(t[k]) for t in trees]), dtype=ty) for k, ty in kinds]
+
+    def forest_predict(self, trees, K: int, votes: bool = False):
+        """Host-pointer form (psgd_forest_predict): (classes int32 [local rows], votes [local rows, K] or None)."""
+        import numpy as np
+        arr = self._forest_nodes(trees)
+        n = self.local_rows()
+        cls = np.zeros(max(n, 1), dtype=np.int32)
+        vt = np.zeros((max(n, 1), int(K)), dtype=np.int32) if votes else None
+        check(self._L.psgd_forest_predict(self.handle, len(trees), *[a.ctypes.data for a in arr], int(K), cls.ctypes.data,
+                                          None if vt is None else vt.ctypes.data))
+        return cls[:n], None if vt is None else vt[:n]
+
+    def forest_predict_device(self, trees, K: int, cls_ptr, votes_ptr, stream=None):
+        """psgd_forest_predict_device: classes / votes (0: none) of the local rows on the device."""
+        arr = self._forest_nodes(trees)
+        check(self._L.psgd_forest_predict_device(self.handle, len(trees), *[a.ctypes.data for a in arr], int(K), cls_ptr,
+                                                 votes_ptr or None, stream))
 
     # Gaussian mixture ---------------------------------------------------------------------------
     def gmm_responsibilities(self, A, b, c, mahalanobis: bool = False):

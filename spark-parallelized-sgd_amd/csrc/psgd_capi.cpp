@@ -3697,6 +3697,228 @@ int32_t psgd_tree_plan(int32_t storage, int32_t d, int32_t max_bins, int32_t num
     return PSGD_OK;
 }
 
+// ---- Random-forest classifier (kernels in psgd_forest.hip; the split pass in psgd_tree.hip) ----
+// The same place in the context as the tree calls. The frontier arrays are the caller's device buffers.
+static int32_t forest_bag_of(uint64_t seed, const uint64_t* cut, int64_t row0, int32_t tree0, psgd::ForestBag* bag) {
+    if (!cut) return fail(PSGD_EINVAL, "cut is null");
+    if (row0 < 0 || tree0 < 0) return fail(PSGD_EINVAL, "row0 and tree0 must be >= 0");
+    for (int k = 0; k < 15; ++k) {
+        if (k > 0 && cut[k] < cut[k - 1]) return fail(PSGD_EINVAL, "cut must ascend");
+        bag->cut[k] = cut[k];
+    }
+    bag->seed = seed;
+    bag->row0 = row0;
+    bag->tree0 = tree0;
+    return PSGD_OK;
+}
+
+int32_t psgd_forest_bag_device(psgd_ctx* ctx, uint64_t seed, const uint64_t* cut, int64_t row0, int32_t tree0, int32_t n_trees,
+                               uint8_t* d_weights, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_weights) return fail(PSGD_EINVAL, "d_weights is null");
+    if (n_trees < 1 || n_trees > 65535) return fail(PSGD_EINVAL, "n_trees must be in [1, 65535]");
+    psgd::ForestBag bag;
+    int32_t rc = forest_bag_of(seed, cut, row0, tree0, &bag);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);   // (the row count is the registry's)
+    if (rc) return rc;
+    const int e = psgd::launch_forest_bag(bag, n_trees, ctx->row_off.back(), d_weights, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("forest bag launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_forest_histogram_device(psgd_ctx* ctx, const uint8_t* d_bins, const uint8_t* d_labels, const int32_t* d_slot,
+                                     int32_t n_trees, const int32_t* d_node_tree, const int32_t* d_tree_base,
+                                     const int32_t* d_sub, int32_t n_frontier, int32_t m, int32_t num_classes, int32_t max_bins,
+                                     int32_t node0, int32_t n_nodes, uint64_t seed, const uint64_t* cut, int64_t row0,
+                                     int32_t tree0, int64_t* d_hist, int64_t* d_nbad, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_bins || !d_labels || !d_slot || !d_node_tree || !d_tree_base || !d_sub || !d_hist || !d_nbad)
+        return fail(PSGD_EINVAL, "d_bins/d_labels/d_slot/d_node_tree/d_tree_base/d_sub/d_hist/d_nbad are null");
+    int32_t rc = tree_args(max_bins, num_classes);
+    if (rc) return rc;
+    if (n_trees < 1 || m < 1) return fail(PSGD_EINVAL, "n_trees and m must be positive");
+    if (node0 < 0 || n_nodes < 1 || node0 > n_frontier - n_nodes)
+        return fail(PSGD_EINVAL, "the nodes node0 .. node0 + n_nodes - 1 must lie in the frontier");
+    if (!aligned16(d_bins)) return fail(PSGD_EINVAL, "d_bins must be 16-byte aligned");
+    psgd::ForestBag bag;
+    rc = forest_bag_of(seed, cut, row0, tree0, &bag);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = tree_rows(ctx);
+    if (rc) return rc;
+    const int32_t d = ctx->parts.begin()->second.d;
+    if (m > d) return fail(PSGD_EINVAL, "m exceeds the rows' features");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    const int64_t n_rows = ctx->row_off.back();
+    const psgd::ForestGeom gm = psgd::forest_geometry(d, max_bins, num_classes, m, n_nodes,
+                                                      (n_rows + psgd::kTreeTileRows - 1) / psgd::kTreeTileRows, INT64_MAX);
+    const int e = psgd::launch_forest_hist(d_bins, d_labels, d_slot, n_rows, n_rows, gm, bag, d_node_tree, d_tree_base, n_trees,
+                                           d_sub, node0, n_nodes, d_hist, d_nbad, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("forest histogram launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_forest_best_split_device(psgd_ctx* ctx, const int64_t* d_hist, const double* d_thresholds, const int32_t* d_nbins,
+                                      const int32_t* d_sub, int32_t m, int32_t max_bins, int32_t num_classes, int32_t n_nodes,
+                                      int32_t impurity, int64_t min_instances, double min_info_gain, double* d_rec,
+                                      void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_hist || !d_thresholds || !d_nbins || !d_sub || !d_rec)
+        return fail(PSGD_EINVAL, "d_hist/d_thresholds/d_nbins/d_sub/d_rec are null");
+    const int32_t rc = tree_args(max_bins, num_classes);
+    if (rc) return rc;
+    if (m < 1 || n_nodes < 1) return fail(PSGD_EINVAL, "m and n_nodes must be positive");
+    if (impurity != PSGD_TREE_GINI && impurity != PSGD_TREE_ENTROPY)
+        return fail(PSGD_EINVAL, "unknown impurity " + std::to_string(impurity));
+    if (min_instances < 1 || !(min_info_gain >= 0.0))
+        return fail(PSGD_EINVAL, "min_instances must be >= 1 and min_info_gain >= 0");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int e = psgd::launch_forest_best_split(d_hist, d_thresholds, d_nbins, d_sub, m, max_bins, num_classes, n_nodes,
+                                                 impurity, (double)min_instances, min_info_gain, d_rec, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("forest split launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_forest_route_device(psgd_ctx* ctx, const uint8_t* d_bins, const int32_t* d_table, const int32_t* d_tree_base,
+                                 int32_t n_trees, int32_t* d_slot, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_bins || !d_table || !d_tree_base || !d_slot) return fail(PSGD_EINVAL, "d_bins/d_table/d_tree_base/d_slot are null");
+    if (n_trees < 1) return fail(PSGD_EINVAL, "n_trees must be positive");
+    if (!aligned16(d_table)) return fail(PSGD_EINVAL, "d_table must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int32_t rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    const int32_t d = ctx->parts.begin()->second.d;
+    const int64_t n_rows = ctx->row_off.back();
+    const int e = psgd::launch_forest_route(d_bins, 16 * ((d + 15) / 16), n_rows, d_table, d_tree_base, n_trees, d_slot, n_rows,
+                                            ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("forest routing launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+namespace {
+struct ForestNodeRec {   // psgd_forest.hip's ForestNode
+    double threshold;
+    int32_t feature, left, right, pad;
+};
+}  // namespace
+
+int32_t psgd_forest_predict_device(psgd_ctx* ctx, int32_t n_trees, const int32_t* tree_off, const int32_t* feature,
+                                   const double* threshold, const int32_t* left, const int32_t* right,
+                                   const int32_t* prediction, int32_t num_classes, int32_t* d_classes, int32_t* d_votes,
+                                   void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!tree_off || !feature || !threshold || !left || !right || !prediction || !d_classes)
+        return fail(PSGD_EINVAL, "tree_off, a node array or d_classes is null");
+    if (n_trees < 1 || tree_off[0] != 0) return fail(PSGD_EINVAL, "n_trees must be positive and tree_off[0] zero");
+    int32_t rc = tree_args(2, num_classes);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = tree_rows(ctx);
+    if (rc) return rc;
+    const Part& first = ctx->parts.begin()->second;
+    for (int32_t t = 0; t < n_trees; ++t)
+        if (tree_off[t + 1] <= tree_off[t]) return fail(PSGD_EINVAL, "tree " + std::to_string(t) + " has no nodes");
+    const int32_t n_nodes = tree_off[n_trees];
+    // the records, then the trees' roots, in one buffer
+    std::vector<ForestNodeRec> nodes((size_t)n_nodes + ((size_t)n_trees * sizeof(int32_t) + sizeof(ForestNodeRec) - 1) / sizeof(ForestNodeRec));
+    for (int32_t t = 0; t < n_trees; ++t) {
+        const int32_t o = tree_off[t], n = tree_off[t + 1] - o;
+        for (int32_t i = 0; i < n; ++i) {
+            const int32_t q = o + i;
+            const bool leaf = feature[q] < 0;
+            // a child lies after its parent within the tree, so every walk ends; a feature is a column of the rows
+            if (!leaf && (feature[q] >= first.d || left[q] <= i || left[q] >= n || right[q] <= i || right[q] >= n))
+                return fail(PSGD_EINVAL, "node " + std::to_string(i) + " of tree " + std::to_string(t) +
+                                             " has a feature past the rows' or a child that is not a later node");
+            if (leaf && (prediction[q] < 0 || prediction[q] >= num_classes))
+                return fail(PSGD_EINVAL, "a leaf of tree " + std::to_string(t) + " predicts a class outside [0, num_classes)");
+            nodes[(size_t)q] = leaf ? ForestNodeRec{0.0, -1, prediction[q], 0, 0}
+                                    : ForestNodeRec{threshold[q], feature[q], o + left[q], o + right[q], 0};
+        }
+    }
+    std::memcpy(nodes.data() + n_nodes, tree_off, (size_t)n_trees * sizeof(int32_t));
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    HIP_TRY(ctx->tnodes.ensure(nodes.size() * sizeof(ForestNodeRec)));
+    HIP_TRY(hipMemcpyAsync(ctx->tnodes.p, nodes.data(), nodes.size() * sizeof(ForestNodeRec), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // the records leave a host vector of this call
+    const int P = (int)ctx->parts.size();
+    const int32_t* d_root = reinterpret_cast<const int32_t*>(static_cast<const ForestNodeRec*>(ctx->tnodes.p) + n_nodes);
+    const int e = psgd::launch_forest_predict(ctx->descs.as<psgd::ChainDesc>(), ctx->cidx.as<int64_t>() + P, P,
+                                              ctx->row_off.back(), first.dtype == PSGD_F32 ? 1 : 0, ctx->tnodes.p, d_root,
+                                              n_trees, num_classes, d_classes, d_votes, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("forest prediction launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_forest_predict(psgd_ctx* ctx, int32_t n_trees, const int32_t* tree_off, const int32_t* feature,
+                            const double* threshold, const int32_t* left, const int32_t* right, const int32_t* prediction,
+                            int32_t num_classes, int32_t* classes, int32_t* votes) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!classes) return fail(PSGD_EINVAL, "classes is null");
+    int32_t rc = tree_args(2, num_classes);
+    if (rc) return rc;
+    size_t n = 0;
+    int32_t* d_cls = nullptr;
+    int32_t* d_votes = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (ctx->parts.empty()) return fail(PSGD_ESTATE, "no partitions registered");
+        for (auto& kv : ctx->parts) n += (size_t)kv.second.n_rows;
+        DeviceGuard g(ctx->device);
+        rc = scratch_acquire(ctx, ctx->stream);
+        if (rc) return rc;
+        const size_t rows = std::max<size_t>(n, 1);
+        HIP_TRY(ctx->tio.ensure(rows * (size_t)(1 + num_classes) * sizeof(int32_t)));
+        d_cls = ctx->tio.as<int32_t>();
+        d_votes = d_cls + rows;
+    }
+    rc = psgd_forest_predict_device(ctx, n_trees, tree_off, feature, threshold, left, right, prediction, num_classes, d_cls,
+                                    votes ? d_votes : nullptr, ctx->stream);
+    if (rc || n == 0) return rc;
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipMemcpyAsync(classes, d_cls, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (votes) HIP_TRY(hipMemcpyAsync(votes, d_votes, n * (size_t)num_classes * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return PSGD_OK;
+}
+
+int32_t psgd_forest_plan(int32_t d, int32_t max_bins, int32_t num_classes, int32_t m, int32_t nodes, int32_t n_trees,
+                         int64_t total_tiles, int64_t n_rows, int64_t scratch_budget, int64_t slot_budget, int64_t* out) {
+    if (!out) return fail(PSGD_EINVAL, "out is null");
+    if (d <= 0 || m < 1 || m > d || nodes < 1 || n_trees < 1 || total_tiles < 0 || n_rows < 0)
+        return fail(PSGD_EINVAL, "d, nodes and n_trees must be positive, 1 <= m <= d, total_tiles and n_rows >= 0");
+    const int32_t rc = tree_args(max_bins, num_classes);
+    if (rc) return rc;
+    if (scratch_budget <= 0) scratch_budget = PSGD_TREE_SCRATCH_BUDGET;
+    if (slot_budget <= 0) slot_budget = PSGD_FOREST_SLOT_BUDGET;
+    const psgd::ForestGeom gm = psgd::forest_geometry(d, max_bins, num_classes, m, nodes, total_tiles, scratch_budget);
+    const int64_t per_tree = std::max<int64_t>(n_rows, 1) * (int64_t)sizeof(int32_t);
+    const int64_t group_trees = std::max<int64_t>(1, std::min<int64_t>(n_trees, slot_budget / per_tree));
+    const int64_t v[PSGD_FOREST_PLAN_LEN] = {gm.jchunk,  gm.sgroup,    gm.lds_bytes, gm.n_groups,  gm.scratch_bytes, gm.group_nodes,
+                                             gm.n_items, gm.span_rows, group_trees,  gm.tile_rows, gm.pitch};
+    std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
 // ---- One EM step of a Gaussian mixture (kernels in psgd_gmm.hip) ----
 // The same place in the context as k-means: score_prepare, the tile table in ctx->stab, the scratch in
 // ctx->qrec, a step's responsibilities in ctx->mixresp, no epoch state touched.

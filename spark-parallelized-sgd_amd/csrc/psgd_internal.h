@@ -575,6 +575,54 @@ int launch_tree_route(const uint8_t* bins, int pitch, int64_t n_rows, const int3
 int launch_tree_predict(const ChainDesc* descs, const int64_t* row_off, int n_parts, int64_t n_rows, int storage,
                         const void* nodes, int n_nodes, int32_t* cls, double* prob, int num_cus, hipStream_t st);
 
+// ---- Random-forest classifier (psgd_forest.hip: psgd_forest_*) ----
+// The plan of a level's histogram pass over a frontier of `nodes` nodes with m subset features each: host
+// code, no device (psgd_forest_plan reports it).
+constexpr int kForestLdsCells = 32768;   // (node, subset position) pairs x (bins classes + 1) words of LDS: 128 KiB
+struct ForestGeom {
+    int32_t d, bins, classes, m;
+    int32_t pitch;                 // bytes of a binned row: d rounded up to 16
+    int32_t jchunk;                // subset positions an item counts (m, or fewer when one node's cells exceed LDS)
+    int32_t sgroup;                // nodes an item counts
+    int32_t n_jchunks, n_sgroups;  // subset chunks of a node, node sub-groups of a group
+    int32_t group_nodes, n_groups; // nodes whose 64-bit table fits the budget, launches a level
+    int32_t tile_rows, tile_log2;  // rows of the LDS row tile (a power of two) and its log2
+    int32_t staged;                // 1: the tile is staged in LDS; 0: a row exceeds it, bytes come through L2
+    int64_t list_off;              // words before the entry list in LDS
+    int64_t span_rows, n_spans;    // rows a span (whole tiles of 256), spans
+    int64_t n_items;               // spans x subset chunks x sub-groups
+    int64_t lds_bytes;             // dynamic LDS of the launch
+    int64_t scratch_bytes;         // the 64-bit table of a group
+};
+struct ForestBag {                 // what the bag weight of (tree, row) is computed from
+    unsigned long long seed;
+    int64_t row0;                  // the global index of the first local row
+    int64_t tree0;                 // the forest's index of the group's tree 0
+    unsigned long long cut[15];    // ascending: the weight is the number of k with u >= cut[k]
+};
+ForestGeom forest_geometry(int d, int bins, int classes, int m, int nodes, int64_t n_tiles, int64_t budget);
+// w [n_trees][n_rows] bytes: the bag weights of trees bag.tree0 .. of the local rows.
+int launch_forest_bag(const ForestBag& bag, int n_trees, int64_t n_rows, uint8_t* w, int num_cus, hipStream_t st);
+// hist [n_nodes][m][bins][classes] (zeroed here) of frontier nodes node0 .. node0 + n_nodes - 1: node_tree [A]
+// (ascending), tree_base [n_trees + 1], sub [A][m], slot [n_trees][slot_ld]; *nbad += the local rows whose
+// label byte is >= classes.
+int launch_forest_hist(const uint8_t* bins, const uint8_t* labels, const int32_t* slot, int64_t slot_ld, int64_t n_rows,
+                       const ForestGeom& gm, const ForestBag& bag, const int32_t* node_tree, const int32_t* tree_base,
+                       int n_trees, const int32_t* sub, int node0, int n_nodes, int64_t* hist, int64_t* nbad,
+                       hipStream_t st);
+// tree_best_split over hist [n_nodes][m][bins][classes] with feature sub[node][j] at position j (psgd_tree.hip).
+int launch_forest_best_split(const int64_t* hist, const double* thr, const int32_t* nbins, const int32_t* sub, int m,
+                             int bins, int classes, int n_nodes, int impurity, double min_inst, double min_gain,
+                             double* rec, hipStream_t st);
+// slot[t][r] <- table[tree_base[t] + slot[t][r]]'s left or right ({feature, bin, left, right}; feature < 0: -1).
+int launch_forest_route(const uint8_t* bins, int pitch, int64_t n_rows, const int32_t* table, const int32_t* tree_base,
+                        int n_trees, int32_t* slot, int64_t slot_ld, int num_cus, hipStream_t st);
+// cls [n_rows] / votes [n_rows][classes] (nullable): nodes are records of 24 bytes {threshold, feature (-1: a
+// leaf), left (a leaf's class), right, pad} with children as indices of the concatenated array; root [n_trees].
+int launch_forest_predict(const ChainDesc* descs, const int64_t* row_off, int n_parts, int64_t n_rows, int storage,
+                          const void* nodes, const int32_t* root, int n_trees, int classes, int32_t* cls, int32_t* votes,
+                          int num_cus, hipStream_t st);
+
 // w_out = updater.compute(w, sum[0 .. d) / sum[d + 1], ..) with s = stepSize / sqrt(iter); *regval
 // the new regVal; part [gd_update_blocks(d)] is scratch. w_out may be w. -2: not Simple / SquaredL2 / L1.
 int64_t gd_update_blocks(int d);

@@ -220,9 +220,13 @@ __device__ __forceinline__ bool tree_better(double ga, int fa, int ba, double gb
 // rec [n_slots][6 + 2 K] = {feature (-1: a leaf), bin, threshold, gain, impurity, n, tot[K], L[K]}.
 // The classes are walked twice a step of 64 bins -- once for nL, once for the impurities, which need nL --
 // with tot and the steps' carries in LDS, so that no per-class array lives in registers.
+// SUB (the forest's pass): the slot's table holds d = m positions, position j being feature sub[slot][j]
+// (ascending, so the tie rule over positions is the tie rule over features); the record names the feature.
+template <bool SUB>
 __global__ __launch_bounds__(kTreeBlock) void tree_best_split(const unsigned long long* __restrict__ hist,
                                                               const double* __restrict__ thr,
-                                                              const int32_t* __restrict__ nbins, int d, int B, int K,
+                                                              const int32_t* __restrict__ nbins,
+                                                              const int32_t* __restrict__ sub, int d, int B, int K,
                                                               int kind, double min_inst, double min_gain,
                                                               double* __restrict__ rec) {
     __shared__ double tot_s[kTreeMaxClasses];
@@ -248,8 +252,9 @@ __global__ __launch_bounds__(kTreeBlock) void tree_best_split(const unsigned lon
     double* carry = carry_s[wave];                       // (every lane stores the same value: the wave's own)
     double bg = 0.0;
     int bf = -1, bb = -1;
+    const int32_t* feat = SUB ? sub + (int64_t)slot * d : nullptr;
     for (int f = wave; f < d; f += kTreeWaves) {
-        int ncand = nbins[f] - 1;                        // candidates: bins 0 .. nb_f - 2
+        int ncand = nbins[SUB ? feat[f] : f] - 1;        // candidates: bins 0 .. nb_f - 2
         ncand = ncand > B - 1 ? B - 1 : ncand;
         const unsigned long long* Hf = H + (int64_t)f * BK;
         for (int c = 0; c < K; ++c) carry[c] = 0.0;
@@ -298,9 +303,10 @@ __global__ __launch_bounds__(kTreeBlock) void tree_best_split(const unsigned lon
         const bool split = w.f >= 0 && w.gain > 0.0 && w.gain >= min_gain;
         win_s[0] = split ? w.f : -1;
         win_s[1] = split ? w.b : -1;
-        out[0] = split ? (double)w.f : -1.0;
+        const int wf = split && SUB ? feat[w.f] : w.f;
+        out[0] = split ? (double)wf : -1.0;
         out[1] = split ? (double)w.b : -1.0;
-        out[2] = split ? thr[(int64_t)w.f * (B - 1) + w.b] : 0.0;
+        out[2] = split ? thr[(int64_t)wf * (B - 1) + w.b] : 0.0;
         out[3] = w.f >= 0 ? w.gain : 0.0;
         out[4] = imp_t;
         out[5] = n;
@@ -450,8 +456,17 @@ int launch_tree_hist(const uint8_t* bins, const uint8_t* labels, const int32_t* 
 int launch_tree_best_split(const int64_t* hist, const double* thr, const int32_t* nbins, int d, int bins, int classes,
                            int n_slots, int impurity, double min_inst, double min_gain, double* rec, hipStream_t st) {
     const unsigned long long* H = reinterpret_cast<const unsigned long long*>(hist);
-    hipLaunchKernelGGL(tree_best_split, dim3((unsigned)n_slots), dim3(kTreeBlock), 0, st, H, thr, nbins, d, bins, classes,
-                       impurity, min_inst, min_gain, rec);
+    hipLaunchKernelGGL(tree_best_split<false>, dim3((unsigned)n_slots), dim3(kTreeBlock), 0, st, H, thr, nbins,
+                       (const int32_t*)nullptr, d, bins, classes, impurity, min_inst, min_gain, rec);
+    return (int)hipGetLastError();
+}
+
+int launch_forest_best_split(const int64_t* hist, const double* thr, const int32_t* nbins, const int32_t* sub, int m,
+                             int bins, int classes, int n_nodes, int impurity, double min_inst, double min_gain,
+                             double* rec, hipStream_t st) {
+    const unsigned long long* H = reinterpret_cast<const unsigned long long*>(hist);
+    hipLaunchKernelGGL(tree_best_split<true>, dim3((unsigned)n_nodes), dim3(kTreeBlock), 0, st, H, thr, nbins, sub, m, bins,
+                       classes, impurity, min_inst, min_gain, rec);
     return (int)hipGetLastError();
 }
 

@@ -1033,6 +1033,147 @@ class HipEngine(ShardedEngine):
             return cls[:n], None if prob is None else prob[:n]
         return self._tree_run(call)
 
+    # random forest (psgd_forest_*_device; tree.py) -------------------------------------------------
+    def _forest_row0(self) -> int:
+        """The global index of this rank's first row: the rows of the partitions before its own."""
+        counts = getattr(self._data, "partition_counts", None)
+        if counts is None:
+            counts = [p.n_rows for p in self._data.partitions]
+        return int(np.sum(counts[: self.lo], dtype=np.int64))
+
+    def forest_bag(self, seed: int, cut, trees=(0, 1)):
+        """The bag weights of trees (first, count) over this rank's rows: a device uint8 tensor [count,
+        local_rows()] (psgd_forest_bag_device; tree.forest_cut makes `cut`). For tests and tools: the training
+        passes recompute the weights."""
+        torch = self.torch
+        t0, nt, n = int(trees[0]), int(trees[1]), self.local_rows()
+        c = np.ascontiguousarray(cut, dtype=np.uint64)
+        if c.shape != (15,):
+            raise IllegalArgumentException(f"requirement failed: cut must hold 15 thresholds (got {c.shape})")
+
+        def call(run):
+            w = torch.zeros(nt * max(n, 1), dtype=torch.uint8, device=self.dev)
+            if run:
+                self.ctx.forest_bag_device(seed, c, self._forest_row0(), t0, nt, w.data_ptr(), self.stream.cuda_stream)
+            return w[: nt * n].view(nt, n)
+        return self._tree_run(call)
+
+    def forest_slots(self, G: int):
+        """slot[t][r] of a group of G trees before the first level: zeros (int32 [G, local_rows()], on the device)."""
+        n = self.local_rows()
+        with self.torch.cuda.stream(self.stream):
+            t = self.torch.zeros(int(G) * max(n, 1), dtype=self.torch.int32, device=self.dev)
+        self.stream.synchronize()
+        return t[: int(G) * n].view(int(G), n)
+
+    def forest_frontier(self, node_tree, tree_base, sub):
+        """A level's frontier on the device (tree.ForestFrontier) from host arrays: node_tree [A] ascending,
+        tree_base [G + 1] with tree t's nodes at tree_base[t] .. tree_base[t + 1] - 1, sub [A, m] each row
+        ascending within [0, num_features)."""
+        from .tree import ForestFrontier
+        torch = self.torch
+        nt = np.ascontiguousarray(node_tree, dtype=np.int32)
+        tb = np.ascontiguousarray(tree_base, dtype=np.int32)
+        sb = np.ascontiguousarray(sub, dtype=np.int32)
+        A = len(nt)
+        ok = (A >= 1 and sb.ndim == 2 and sb.shape[0] == A and 1 <= sb.shape[1] <= self._data.num_features and len(tb) >= 2
+              and tb[0] == 0 and tb[-1] == A and (np.diff(tb) >= 0).all()
+              and (nt == np.repeat(np.arange(len(tb) - 1), np.diff(tb))).all()
+              and sb.min() >= 0 and sb.max() < self._data.num_features and (np.diff(sb, axis=1) > 0).all())
+        if not ok:
+            raise IllegalArgumentException("requirement failed: the frontier's node_tree, tree_base and sub do not agree")
+        with torch.cuda.stream(self.stream):
+            out = ForestFrontier(*(torch.from_numpy(a.copy()).to(self.dev) for a in (nt, tb, sb)))
+        self.stream.synchronize()
+        return out
+
+    def forest_histogram(self, bins, slots, K: int, frontier, bag, group=None):
+        """H[node][j][b][c] of the frontier's nodes `group` = (first node, nodes) -- default: all -- over every row
+        of the data, on all ranks: a device int64 tensor [nodes, m, maxBins, K] of bag-weighted counts
+        (psgd_forest_histogram_device). bag = (seed, the forest's index of the group's first tree, cut). The
+        ranks add their tables with an integer all-reduce, as tree_histogram does."""
+        torch = self.torch
+        A, m = (int(v) for v in frontier.sub.shape)
+        a0, na = (0, A) if group is None else (int(group[0]), int(group[1]))
+        G, B = int(slots.shape[0]), bins.max_bins
+        seed, tree0, cut = int(bag[0]), int(bag[1]), np.ascontiguousarray(bag[2], dtype=np.uint64)
+        if G != frontier.tree_base.shape[0] - 1 or cut.shape != (15,):
+            raise IllegalArgumentException("requirement failed: slots must hold one row per tree of the frontier, cut 15 thresholds")
+
+        def call(run):
+            buf = torch.zeros(1 + na * m * B * K, dtype=torch.int64, device=self.dev)   # {n_bad, H}
+            if run:
+                self.ctx.forest_histogram_device(bins.bins.data_ptr(), bins.labels.data_ptr(), slots.data_ptr(), G,
+                                                 frontier.node_tree.data_ptr(), frontier.tree_base.data_ptr(),
+                                                 frontier.sub.data_ptr(), A, m, K, B, a0, na, seed, cut, self._forest_row0(),
+                                                 tree0, buf.data_ptr() + 8, buf.data_ptr(), self.stream.cuda_stream)
+            if self.world > 1:
+                import torch.distributed as dist
+                if dist.get_backend() == "gloo":   # (through the host: gloo takes CPU tensors)
+                    h = buf.cpu()
+                    dist.all_reduce(h)
+                    buf = h.to(self.dev)
+                else:
+                    dist.all_reduce(buf)
+            return buf
+        buf = self._tree_run(call)
+        bad = int(buf[:1].cpu().numpy()[0])
+        if bad > 0:
+            raise IllegalArgumentException(f"requirement failed: {bad} labels are not whole numbers in [0, {K})")
+        return buf[1:].view(na, m, B, K)
+
+    def forest_best_split(self, hist, bins, frontier, node0: int = 0, impurity: str = "gini", minInstancesPerNode: int = 1,
+                          minInfoGain: float = 0.0):
+        """One record a node of `hist` [nodes, m, maxBins, K], whose first node is the frontier's node0
+        (psgd_forest_best_split_device): tree_best_split's record, the feature field the real feature."""
+        torch = self.torch
+        na, m, B, K = (int(v) for v in hist.shape)
+        if m != frontier.sub.shape[1] or node0 < 0 or node0 + na > frontier.sub.shape[0]:
+            raise IllegalArgumentException("requirement failed: hist does not match the frontier's nodes")
+
+        def call(_run):
+            rec = torch.zeros((na, 6 + 2 * K), dtype=torch.float64, device=self.dev)
+            self.ctx.forest_best_split_device(hist.data_ptr(), bins.thresholds.data_ptr(), bins.nbins.data_ptr(),
+                                              frontier.sub.data_ptr() + 4 * node0 * m, m, B, K, na,
+                                              N.TREE_IMPURITIES[impurity], minInstancesPerNode, minInfoGain, rec.data_ptr(),
+                                              self.stream.cuda_stream)
+            return rec
+        return self._tree_run(call, rows=False)
+
+    def forest_route(self, bins, slots, frontier, table):
+        """slots[t][r] <- the child's slot within tree t's next frontier, from `table` [A, 4] int32 {feature,
+        bin, left, right} over the whole frontier (a host array; feature -1: a leaf), in place
+        (psgd_forest_route_device)."""
+        torch = self.torch
+        tab = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, 4)
+        if tab.shape[0] != frontier.sub.shape[0]:
+            raise IllegalArgumentException("requirement failed: the table must hold one row per node of the frontier")
+
+        def call(run):
+            d_tab = torch.from_numpy(tab.copy()).to(self.dev)
+            if run and slots.numel() > 0:
+                self.ctx.forest_route_device(bins.bins.data_ptr(), d_tab.data_ptr(), frontier.tree_base.data_ptr(),
+                                             int(slots.shape[0]), slots.data_ptr(), self.stream.cuda_stream)
+            self.stream.synchronize()   # d_tab is a temporary of this call
+            return slots
+        return self._tree_run(call)
+
+    def forest_predict(self, trees, K: int, votes: bool = False):
+        """(classes, votes) of every row of this rank's partitions under the forest `trees` (a list of node
+        mappings as tree_predict takes): device int32 tensors [local_rows()] and [local_rows(), K]
+        (psgd_forest_predict_device; votes is None unless asked for)."""
+        torch = self.torch
+        n = self.local_rows()
+
+        def call(run):
+            cls = torch.zeros(max(n, 1), dtype=torch.int32, device=self.dev)
+            vt = torch.zeros((max(n, 1), int(K)), dtype=torch.int32, device=self.dev) if votes else None
+            if run:
+                self.ctx.forest_predict_device(trees, K, cls.data_ptr(), 0 if vt is None else vt.data_ptr(),
+                                               self.stream.cuda_stream)
+            return cls[:n], None if vt is None else vt[:n]
+        return self._tree_run(call)
+
     # Gaussian mixture (psgd_gmm_*_device; clustering.py) -------------------------------------------
     def _gmm_operands(self, weights, gaussians):
         """(k, [A | b | c] as one f64 device tensor) of a mixture of stat.MultivariateGaussian components

@@ -16,15 +16,29 @@ table exceeds scratchBudget bytes is processed in groups of slots (psgd_tree_pla
 
 The row sample of find_splits is this project's convention, as in KMeans: every row while n <=
 max(maxBins^2, 10,000), else that many distinct positions from numpy.random.default_rng(seed), read as the
-engine registered them. Regression trees, categorical features and forests are not built."""
+engine registered them. Regression trees and categorical features are not built.
+
+RandomForest.trainClassifier trains numTrees such trees on bagged rows, each node looking at a random subset
+of the features (include/psgd.h has the bag weight; forest_cut, forest_subset_size and forest_subset are the
+host's part of the definitions):
+
+  forest = RandomForest.trainClassifier(data, numClasses=3, numTrees=20, seed=7)
+  forest.trees, forest.numTrees, forest.totalNumNodes
+  forest.predict(data)                   # the trees' majority vote, ties to the lowest class
+
+The rows are binned once; the trees train in groups of as many as slotBudget bytes of per-tree slots allow, a
+group a level at a time through the forest passes (HipEngine.forest_histogram reads a row once for all trees
+of a node sub-group, adds the bag weight, and counts only the node's feature subset). With more than one
+rank, pass a seed: seed=None draws one on each host."""
 from __future__ import annotations
 
+import math
 from typing import NamedTuple
 
 import numpy as np
 
 from ._native import (TREE_IMPURITIES, TREE_MAX_BINS, TREE_MAX_CLASSES, IllegalArgumentException,
-                      UnsupportedOperationException, tree_plan)
+                      UnsupportedOperationException, forest_plan, tree_plan)
 from .data import PartitionedData
 
 
@@ -152,6 +166,33 @@ class DecisionTreeModel:
         return "\n".join(lines) + "\n"
 
 
+def _check_train_args(data, numClasses, categoricalFeaturesInfo, impurity, maxDepth, maxBins, minInstancesPerNode,
+                      minInfoGain):
+    """trainClassifier's refusals, the tree's and the forest's alike."""
+    if categoricalFeaturesInfo:
+        raise UnsupportedOperationException("categorical features are not built: categoricalFeaturesInfo must be empty")
+    if impurity == "variance":
+        raise UnsupportedOperationException("regression trees are not built: impurity is 'gini' or 'entropy'")
+    if impurity not in TREE_IMPURITIES:
+        raise IllegalArgumentException(f"requirement failed: unknown impurity {impurity!r}")
+    K = numClasses
+    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 2:
+        raise IllegalArgumentException(f"requirement failed: numClasses must be an integer >= 2 (got {K!r})")
+    if K > TREE_MAX_CLASSES:
+        raise UnsupportedOperationException(f"a tree takes at most {TREE_MAX_CLASSES} classes (got {K})")
+    if isinstance(maxDepth, (bool, np.bool_)) or int(maxDepth) < 0:
+        raise IllegalArgumentException(f"requirement failed: maxDepth must be nonnegative but got {maxDepth!r}")
+    if int(maxDepth) > 30:
+        raise UnsupportedOperationException(f"DecisionTree currently only supports maxDepth <= 30, but was given {maxDepth}")
+    if int(maxBins) > TREE_MAX_BINS:
+        raise UnsupportedOperationException(f"a tree takes at most {TREE_MAX_BINS} bins (got {maxBins}): a bin is a byte")
+    if int(minInstancesPerNode) < 1 or not float(minInfoGain) >= 0.0:
+        raise IllegalArgumentException("requirement failed: minInstancesPerNode must be >= 1 and minInfoGain >= 0")
+    _check_dense(data)
+    if data.num_partitions == 0:
+        raise IllegalArgumentException("requirement failed: Cannot train a tree on data without partitions.")
+
+
 class DecisionTree:
     """MLlib 1.6.1 DecisionTree (the module docstring has the loop)."""
 
@@ -159,28 +200,9 @@ class DecisionTree:
     def trainClassifier(data: PartitionedData, numClasses: int, categoricalFeaturesInfo=None, impurity: str = "gini",
                         maxDepth: int = 5, maxBins: int = 32, minInstancesPerNode: int = 1, minInfoGain: float = 0.0,
                         seed=None, *, engine=None, scratchBudget: int = 0) -> DecisionTreeModel:
-        if categoricalFeaturesInfo:
-            raise UnsupportedOperationException("categorical features are not built: categoricalFeaturesInfo must be empty")
-        if impurity == "variance":
-            raise UnsupportedOperationException("regression trees are not built: impurity is 'gini' or 'entropy'")
-        if impurity not in TREE_IMPURITIES:
-            raise IllegalArgumentException(f"requirement failed: unknown impurity {impurity!r}")
+        _check_train_args(data, numClasses, categoricalFeaturesInfo, impurity, maxDepth, maxBins, minInstancesPerNode,
+                          minInfoGain)
         K = numClasses
-        if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 2:
-            raise IllegalArgumentException(f"requirement failed: numClasses must be an integer >= 2 (got {K!r})")
-        if K > TREE_MAX_CLASSES:
-            raise UnsupportedOperationException(f"a tree takes at most {TREE_MAX_CLASSES} classes (got {K})")
-        if isinstance(maxDepth, (bool, np.bool_)) or int(maxDepth) < 0:
-            raise IllegalArgumentException(f"requirement failed: maxDepth must be nonnegative but got {maxDepth!r}")
-        if int(maxDepth) > 30:
-            raise UnsupportedOperationException(f"DecisionTree currently only supports maxDepth <= 30, but was given {maxDepth}")
-        if int(maxBins) > TREE_MAX_BINS:
-            raise UnsupportedOperationException(f"a tree takes at most {TREE_MAX_BINS} bins (got {maxBins}): a bin is a byte")
-        if int(minInstancesPerNode) < 1 or not float(minInfoGain) >= 0.0:
-            raise IllegalArgumentException("requirement failed: minInstancesPerNode must be >= 1 and minInfoGain >= 0")
-        _check_dense(data)
-        if data.num_partitions == 0:
-            raise IllegalArgumentException("requirement failed: Cannot train a tree on data without partitions.")
         K, maxDepth, maxBins = int(K), int(maxDepth), int(maxBins)
         engine = _engine_for(data, engine)
         thr, nbins = find_splits(data, maxBins, seed, engine=engine)
@@ -242,3 +264,167 @@ def _node_arrays(done: dict, K: int) -> dict:
         if node["feature"] >= 0:
             out["left"][i], out["right"][i] = at[2 * nid], at[2 * nid + 1]
     return out
+
+
+# ---- random forest ----------------------------------------------------------------------------------------
+FOREST_STRATEGIES = ("auto", "all", "sqrt", "log2", "onethird")
+
+
+class ForestFrontier(NamedTuple):
+    """HipEngine.forest_frontier's result: a level's open nodes of a group of trees, on the device."""
+    node_tree: object     # int32 [A]: the node's tree within the group, ascending
+    tree_base: object     # int32 [G + 1]: tree t's nodes are tree_base[t] .. tree_base[t + 1] - 1
+    sub: object           # int32 [A, m]: the node's feature subset, ascending
+
+
+def forest_cut(numTrees: int, subsamplingRate: float = 1.0) -> np.ndarray:
+    """The 15 ascending uint64 thresholds of the bag weight, cut[k] = ceil(F(k) 2^53) (at most 2^53): Poisson(rate)
+    for numTrees > 1, with F summed in fp64 from term_0 = exp(-rate), term_j = term_{j-1} * rate / j; one tree
+    keeps a row with probability rate (weight 0 or 1), and every row when rate is 1."""
+    top = 1 << 53
+    cut = [top] * 15
+    if numTrees > 1:
+        term, F = math.exp(-float(subsamplingRate)), 0.0
+        for k in range(15):
+            F += term
+            cut[k] = min(top, math.ceil(F * 2.0 ** 53))
+            term = term * float(subsamplingRate) / (k + 1)
+    else:
+        cut[0] = min(top, math.ceil((1.0 - float(subsamplingRate)) * 2.0 ** 53))
+    return np.array(cut, dtype=np.uint64)
+
+
+def forest_subset_size(featureSubsetStrategy: str, d: int, numTrees: int) -> int:
+    """m, the features a node looks at: d ("all"), ceil(sqrt d), max(1, ceil(log2 d)), ceil(d / 3); "auto" is "all"
+    for one tree, else "sqrt"."""
+    kind = featureSubsetStrategy
+    if kind not in FOREST_STRATEGIES:
+        raise IllegalArgumentException(f"requirement failed: unknown featureSubsetStrategy {kind!r}: one of {FOREST_STRATEGIES}")
+    if kind == "auto":
+        kind = "all" if numTrees == 1 else "sqrt"
+    d = int(d)
+    if kind == "sqrt":
+        r = math.isqrt(d)
+        return r if r * r == d else r + 1
+    if kind == "log2":
+        return max(1, (d - 1).bit_length())
+    return d if kind == "all" else -(-d // 3)
+
+
+def forest_subset(seed: int, tree: int, nid: int, d: int, m: int) -> np.ndarray:
+    """The m features (ascending, int32) that node `nid` (MLlib's id) of tree `tree` looks at: a pure function
+    of its arguments."""
+    if m == d:
+        return np.arange(d, dtype=np.int32)
+    return np.sort(np.random.default_rng([int(seed), int(tree), int(nid)]).choice(d, m, replace=False)).astype(np.int32)
+
+
+class RandomForestModel:
+    """The trained trees (DecisionTreeModel each); predict is their majority vote, ties to the lowest class."""
+
+    def __init__(self, trees, numClasses: int, numFeatures: int, seed: int):
+        self.trees, self.numClasses, self.numFeatures, self.seed = list(trees), int(numClasses), int(numFeatures), int(seed)
+
+    @property
+    def numTrees(self) -> int:
+        return len(self.trees)
+
+    @property
+    def totalNumNodes(self) -> int:
+        return sum(t.numNodes for t in self.trees)
+
+    def predict(self, data: PartitionedData, *, engine=None):
+        """The voted class of every row: one device int32 tensor per partition of `data` (empty for another
+        rank's partitions)."""
+        if data.num_features != self.numFeatures:
+            raise IllegalArgumentException(
+                f"requirement failed: vector sizes do not match: Expected {self.numFeatures} but found {data.num_features}")
+        _check_dense(data)
+        engine = _engine_for(data, engine)
+        cls, _ = engine.forest_predict([t.nodes for t in self.trees], self.numClasses)
+        out, at = [], 0
+        for p, part in enumerate(data.partitions):
+            n = part.n_rows if engine.lo <= p < engine.hi else 0
+            out.append(cls[at: at + n])
+            at += n
+        return out
+
+    def toDebugString(self) -> str:
+        lines = [f"TreeEnsembleModel classifier with {self.numTrees} trees", ""]
+        for t, tree in enumerate(self.trees):
+            lines.append(f"  Tree {t}:")
+            lines += ["   " + line for line in tree.toDebugString().splitlines()[1:]]
+        return "\n".join(lines) + "\n"
+
+
+class RandomForest:
+    """MLlib 1.6.1 RandomForest for classification (the module docstring has the loop)."""
+
+    @staticmethod
+    def trainClassifier(data: PartitionedData, numClasses: int, categoricalFeaturesInfo=None, numTrees: int = 20,
+                        featureSubsetStrategy: str = "auto", impurity: str = "gini", maxDepth: int = 4, maxBins: int = 32,
+                        seed=None, *, minInstancesPerNode: int = 1, minInfoGain: float = 0.0, subsamplingRate: float = 1.0,
+                        engine=None, scratchBudget: int = 0, slotBudget: int = 0) -> RandomForestModel:
+        _check_train_args(data, numClasses, categoricalFeaturesInfo, impurity, maxDepth, maxBins, minInstancesPerNode,
+                          minInfoGain)
+        if isinstance(numTrees, (bool, np.bool_)) or not isinstance(numTrees, (int, np.integer)) or numTrees < 1:
+            raise IllegalArgumentException(f"requirement failed: numTrees must be an integer >= 1 (got {numTrees!r})")
+        if not 0.0 < float(subsamplingRate) <= 1.0:
+            raise IllegalArgumentException(f"requirement failed: subsamplingRate must be in (0, 1] (got {subsamplingRate!r})")
+        K, T, maxDepth, maxBins, d = int(numClasses), int(numTrees), int(maxDepth), int(maxBins), data.num_features
+        m = forest_subset_size(featureSubsetStrategy, d, T)
+        seed = int(np.random.default_rng().integers(0, 1 << 63)) if seed is None else int(seed)
+        cut = forest_cut(T, subsamplingRate)
+        engine = _engine_for(data, engine)
+        thr, nbins = find_splits(data, maxBins, seed, engine=engine)
+        bins = engine.tree_bin(thr, nbins)
+        counts = getattr(data, "partition_counts", None)
+        n = int(np.sum(counts)) if counts is not None else data.count()
+        # (the same tree groups on every rank: sized by all the rows, not this rank's)
+        G = forest_plan(d, maxBins, K, m, 1, T, 0, n, scratchBudget, slotBudget)["group_trees"]
+        trees = []
+        for t0 in range(0, T, G):
+            g = min(G, T - t0)
+            slots = engine.forest_slots(g)
+            done = [{} for _ in range(g)]           # per tree: MLlib id -> the node's fields
+            frontier = [[1] for _ in range(g)]      # per tree: the open nodes' ids, in slot order
+            level = 0
+            while any(frontier):
+                flat = [(t, nid) for t in range(g) for nid in frontier[t]]
+                A = len(flat)
+                base = np.concatenate([[0], np.cumsum([len(f) for f in frontier])]).astype(np.int32)
+                sub = np.stack([forest_subset(seed, t0 + t, nid, d, m) for t, nid in flat])
+                fr = engine.forest_frontier(np.array([t for t, _ in flat], dtype=np.int32), base, sub)
+                plan = forest_plan(d, maxBins, K, m, A, g, 0, n, scratchBudget, slotBudget)
+                recs = []
+                for a0 in range(0, A, plan["group_nodes"]):
+                    group = (a0, min(plan["group_nodes"], A - a0))
+                    hist = engine.forest_histogram(bins, slots, K, fr, (seed, t0, cut), group)
+                    recs.append(engine.forest_best_split(hist, bins, fr, a0, impurity, minInstancesPerNode,
+                                                         minInfoGain).cpu().numpy())
+                rec = np.concatenate(recs)
+                table = np.full((A, 4), -1, dtype=np.int32)
+                nxt = [[] for _ in range(g)]
+                for a, (t, nid) in enumerate(flat):
+                    r = rec[a]
+                    tot, L = r[6: 6 + K], r[6 + K: 6 + 2 * K]
+                    split = r[0] >= 0 and level < maxDepth
+                    done[t][nid] = dict(feature=int(r[0]) if split else -1, threshold=float(r[2]) if split else 0.0,
+                                        gain=float(r[3]) if split else 0.0, impurity=float(r[4]), counts=tot.copy(),
+                                        bin=int(r[1]) if split else -1)
+                    if not split:
+                        continue
+                    table[a, 0], table[a, 1] = int(r[0]), int(r[1])
+                    for side, cnt in ((0, L), (1, tot - L)):
+                        cid = 2 * nid + side
+                        if level + 1 >= maxDepth or np.count_nonzero(cnt) <= 1:   # a finished leaf: no slot
+                            done[t][cid] = dict(feature=-1, threshold=0.0, gain=0.0, impurity=_impurity(cnt, impurity),
+                                                counts=cnt.copy(), bin=-1)
+                        else:
+                            table[a, 2 + side] = len(nxt[t])
+                            nxt[t].append(cid)
+                if any(nxt):
+                    engine.forest_route(bins, slots, fr, table)
+                frontier, level = nxt, level + 1
+            trees += [DecisionTreeModel(_node_arrays(done[t], K), K, d) for t in range(g)]
+        return RandomForestModel(trees, K, d, seed)
