@@ -717,6 +717,46 @@ int32_t psgd_tree_predict_device(psgd_ctx* ctx, int32_t n_nodes, const int32_t* 
                                  const int32_t* left, const int32_t* right, const int32_t* prediction,
                                  const double* probability, int32_t* d_classes, double* d_prob, void* stream);
 
+/* A regression tree over the tree's binned rows -- the passes behind DecisionTree.trainRegressor (variance
+ * impurity). The project's own definitions; every accumulated quantity is an exact integer, so every output
+ * has the same bits from call to call, over slot groups and however the rows are spread over ranks.
+ * Labels: the registered ones, or d_y (device doubles, one a local row in local row order) when it is not null.
+ * Range: key(y), in uint64 arithmetic on y's bits u: ~u when the sign bit is set, else u | 2^63 -- a < b exactly
+ *   when key(a) < key(b). psgd_tree_label_range_device writes d_range[3] = {min key, max key, n_bad} over the
+ *   local rows: n_bad counts the NaN and infinite labels, which enter neither key; without a finite label
+ *   min key > max key. Integer min and max: exact in any order. The caller combines ranks with min and max.
+ * Target of a row: q = rint((y - ymin) 2^s) as uint32 -- the subtraction rounds once in fp64, the scaling is
+ *   exact, ties go to even; ymin and ymax are the extremes over all ranks and s is the largest integer with
+ *   (ymax - ymin) 2^s < 2^30 (the difference as fp64 rounds it; 0 for a constant label), so 0 <= q <= 2^30. A bad
+ *   label gets 0. A target's unit is 2^-s: a node of n rows whose targets sum to S predicts
+ *   ymin + S / (n 2^s), within (ymax - ymin) 2^-30 of the mean of its raw labels. The caller keeps the rows of
+ *   all ranks below 2^33 (a single tree: every weight is 1), so that no 64-bit sum passes 2^63.
+ * Moments: d_mom[slot - slot0][4] (int64) = {n, S = sum q, sum (q^2 >> 30), sum (q^2 & (2^30 - 1))} over the
+ *   local rows of the slots slot0 .. slot0 + n_slots - 1; the call zeroes the table first. sum q^2 =
+ *   2^30 [2] + [3]; the node's impurity is (n sum q^2 - S^2) / n^2 in units of 2^-2s.
+ * Histogram: H[slot - slot0][f][b] = {rows, sum q} (two int64; the bin pitch is max_bins) of the local rows with
+ *   that slot and bins[r][f] = b; the call zeroes the table first. Integer adds in LDS (a uint32 count, a 64-bit
+ *   sum), integer atomics into H. replication as in psgd_tree_histogram_device.
+ * Best split of a slot: n and S from d_mom[slot] (the table's first slot is d_hist's). For feature f and
+ *   candidate b in [0, nb_f - 2]: nL, SL = the sums of H[slot][f][b'] over b' <= b, nR = n - nL, SR = S - SL, all
+ *   integers; valid when nL >= min_instances and nR >= min_instances; in fp64, each integer converted once,
+ *   gain = (((SL SL) / nL + (SR SR) / nR - (S S) / n) / n) 2^-2s -- the drop in variance, in the labels' units.
+ *   The winner, the tie rule and the leaf rule are psgd_tree_best_split_device's. d_rec[slot] holds 4 doubles:
+ *   feature (-1: a leaf), bin, threshold, gain (the best valid candidate's, 0 without one).
+ * Routing and prediction are the classifier's calls: a regression model puts a node's value in `probability`.
+ * Errors: those of the classifier's calls; PSGD_EINVAL for |s| > 1100 or a ymin that is not finite. */
+int32_t psgd_tree_label_range_device(psgd_ctx* ctx, const double* d_y, uint64_t* d_range, void* stream);
+int32_t psgd_tree_targets_device(psgd_ctx* ctx, const double* d_y, double ymin, int32_t s, uint32_t* d_q, void* stream);
+int32_t psgd_tree_moments_device(psgd_ctx* ctx, const uint32_t* d_q, const int32_t* d_slot, int32_t slot0, int32_t n_slots,
+                                 int64_t* d_mom, void* stream);
+int32_t psgd_tree_histogram_reg_device(psgd_ctx* ctx, const uint8_t* d_bins, const uint32_t* d_q, const int32_t* d_slot,
+                                       int32_t max_bins, int32_t slot0, int32_t n_slots, int32_t replication,
+                                       int64_t* d_hist, void* stream);
+int32_t psgd_tree_best_split_reg_device(psgd_ctx* ctx, const int64_t* d_hist, const int64_t* d_mom,
+                                        const double* d_thresholds, const int32_t* d_nbins, int32_t d, int32_t max_bins,
+                                        int32_t n_slots, int32_t s, int64_t min_instances, double min_info_gain,
+                                        double* d_rec, void* stream);
+
 /* How psgd_tree_histogram_device runs a frontier of `slots` slots over rows of d features cut into
  * total_tiles tiles of 256 local rows: host code, no device and no context (the storage of the rows does
  * not enter: the pass reads the binned bytes). budget: the bytes the 64-bit table of one launch may take
@@ -730,8 +770,10 @@ int32_t psgd_tree_predict_device(psgd_ctx* ctx, int32_t n_nodes, const int32_t* 
  *   [4] the groups of a level; [5] bytes of the 64-bit table of a group; [6] the slots of a group;
  *   [7] the work items of a launch (spans x feature chunks x sub-groups); [8] the rows of a span;
  *   [9] the pitch of a binned row in bytes.
+ * num_classes = 0 plans psgd_tree_histogram_reg_device: a cell of {count, sum} takes 12 bytes of LDS instead
+ * of 4 a class and 16 bytes of the 64-bit table instead of 8 a class.
  * Errors: PSGD_EINVAL for a null out, an unknown storage, d <= 0, slots < 1, total_tiles < 0, max_bins < 2 or
- * num_classes < 2; PSGD_EUNSUPPORTED past PSGD_TREE_MAX_BINS / PSGD_TREE_MAX_CLASSES. */
+ * num_classes < 2 and not 0; PSGD_EUNSUPPORTED past PSGD_TREE_MAX_BINS / PSGD_TREE_MAX_CLASSES. */
 #define PSGD_TREE_PLAN_LEN 10
 int32_t psgd_tree_plan(int32_t storage, int32_t d, int32_t max_bins, int32_t num_classes, int32_t slots, int64_t total_tiles,
                        int64_t budget, int64_t* out);

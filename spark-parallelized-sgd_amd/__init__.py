@@ -21,8 +21,8 @@ from .gradient_descent import (GradientDescent, GradientSum, gradient_sum, gradi
 from .newton import HessianSum, Newton, hessian_sum, runNewton
 from .clustering import (GaussianMixture, GaussianMixtureModel, GaussianMixtureStep, KMeans, KMeansModel, KMeansStep,
                          gmm_step, kmeans_step)
-from .tree import (DecisionTree, DecisionTreeModel, ForestFrontier, RandomForest, RandomForestModel, TreeBins, find_splits,
-                   forest_cut, forest_subset, forest_subset_size)
+from .tree import (DecisionTree, DecisionTreeModel, ForestFrontier, RandomForest, RandomForestModel, TreeBins, TreeTargets,
+                   find_splits, forest_cut, forest_subset, forest_subset_size, target_scale)
 from .updater import (AdaGradSGDUpdater, AdamSGDUpdater, L1SGDUpdater, SGDUpdater,
                       SimpleSGDUpdater, SquaredL2SGDUpdater)
 from .evaluation import BinaryClassificationMetrics, MulticlassMetrics
@@ -39,7 +39,7 @@ __all__ = [
     "Newton", "runNewton", "hessian_sum", "HessianSum",
     "KMeans", "KMeansModel", "KMeansStep", "kmeans_step",
     "GaussianMixture", "GaussianMixtureModel", "GaussianMixtureStep", "gmm_step", "MultivariateGaussian",
-    "DecisionTree", "DecisionTreeModel", "TreeBins", "find_splits",
+    "DecisionTree", "DecisionTreeModel", "TreeBins", "find_splits", "TreeTargets", "target_scale",
     "RandomForest", "RandomForestModel", "ForestFrontier", "forest_cut", "forest_subset", "forest_subset_size",
     "Gramian", "gramian", "covariance", "corr", "normal_equations",
     "QRFactor", "QRDecomposition", "qr_factor", "least_squares", "tallSkinnyQR",

@@ -44,6 +44,8 @@ EXPORTED = (
     "psgd_kmeans_update_device", "psgd_kmeans_plan",
     "psgd_tree_bin_device", "psgd_tree_histogram_device", "psgd_tree_best_split_device", "psgd_tree_route_device",
     "psgd_tree_predict", "psgd_tree_predict_device", "psgd_tree_plan",
+    "psgd_tree_label_range_device", "psgd_tree_targets_device", "psgd_tree_moments_device",
+    "psgd_tree_histogram_reg_device", "psgd_tree_best_split_reg_device",
     "psgd_forest_bag_device", "psgd_forest_histogram_device", "psgd_forest_best_split_device", "psgd_forest_route_device",
     "psgd_forest_predict", "psgd_forest_predict_device", "psgd_forest_plan",
     "psgd_gmm_responsibilities", "psgd_gmm_responsibilities_device", "psgd_gmm_moments_device",
@@ -193,6 +195,12 @@ def lib():
             "psgd_tree_predict": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_tree_predict_device": ([vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp, vp], C.c_int32),
             "psgd_tree_plan": ([C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, vp], C.c_int32),
+            "psgd_tree_label_range_device": ([vp, vp, vp, vp], C.c_int32),
+            "psgd_tree_targets_device": ([vp, vp, C.c_double, C.c_int32, vp, vp], C.c_int32),
+            "psgd_tree_moments_device": ([vp, vp, vp, C.c_int32, C.c_int32, vp, vp], C.c_int32),
+            "psgd_tree_histogram_reg_device": ([vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp], C.c_int32),
+            "psgd_tree_best_split_reg_device": ([vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                                 C.c_double, vp, vp], C.c_int32),
             "psgd_forest_bag_device": ([vp, C.c_uint64, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp], C.c_int32),
             "psgd_forest_histogram_device": ([vp, vp, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int64, C.c_int32, vp, vp,
@@ -864,6 +872,32 @@ class Context:
         arr = self._tree_nodes(nodes)
         check(self._L.psgd_tree_predict_device(self.handle, len(arr[0]), *[a.ctypes.data for a in arr], cls_ptr,
                                                prob_ptr or None, stream))
+
+    # regression tree ------------------------------------------------------------------------------
+    def tree_label_range_device(self, y_ptr, range_ptr, stream=None):
+        """psgd_tree_label_range_device: range uint64 [3] = {min key, max key, bad labels} (y_ptr 0: the registered labels)."""
+        check(self._L.psgd_tree_label_range_device(self.handle, y_ptr or None, range_ptr, stream))
+
+    def tree_targets_device(self, y_ptr, ymin: float, s: int, q_ptr, stream=None):
+        """psgd_tree_targets_device: q uint32 [local rows] = rint((y - ymin) 2^s)."""
+        check(self._L.psgd_tree_targets_device(self.handle, y_ptr or None, float(ymin), int(s), q_ptr, stream))
+
+    def tree_moments_device(self, q_ptr, slot_ptr, slot0: int, n_slots: int, mom_ptr, stream=None):
+        """psgd_tree_moments_device: mom int64 [n_slots, 4] of slots slot0 .. on the device."""
+        check(self._L.psgd_tree_moments_device(self.handle, q_ptr, slot_ptr, int(slot0), int(n_slots), mom_ptr, stream))
+
+    def tree_histogram_reg_device(self, bins_ptr, q_ptr, slot_ptr, max_bins: int, slot0: int, n_slots: int, replication: int,
+                                  hist_ptr, stream=None):
+        """psgd_tree_histogram_reg_device: hist [n_slots, d, max_bins, 2] int64 {rows, sum q} of slots slot0 .. ."""
+        check(self._L.psgd_tree_histogram_reg_device(self.handle, bins_ptr, q_ptr, slot_ptr, int(max_bins), int(slot0),
+                                                     int(n_slots), int(replication), hist_ptr, stream))
+
+    def tree_best_split_reg_device(self, hist_ptr, mom_ptr, thr_ptr, nb_ptr, d: int, max_bins: int, n_slots: int, s: int,
+                                   min_instances: int, min_info_gain: float, rec_ptr, stream=None):
+        """psgd_tree_best_split_reg_device: rec [n_slots, 4] doubles on the device."""
+        check(self._L.psgd_tree_best_split_reg_device(self.handle, hist_ptr, mom_ptr, thr_ptr, nb_ptr, int(d), int(max_bins),
+                                                      int(n_slots), int(s), int(min_instances), float(min_info_gain),
+                                                      rec_ptr, stream))
 
     # random forest --------------------------------------------------------------------------------
     def forest_bag_device(self, seed: int, cut, row0: int, tree0: int, n_trees: int, w_ptr, stream=None):

@@ -3687,13 +3687,116 @@ int32_t psgd_tree_plan(int32_t storage, int32_t d, int32_t max_bins, int32_t num
     if (!out) return fail(PSGD_EINVAL, "out is null");
     if (storage != PSGD_F64 && storage != PSGD_F32) return fail(PSGD_EINVAL, "unknown storage dtype " + std::to_string(storage));
     if (d <= 0 || slots < 1 || total_tiles < 0) return fail(PSGD_EINVAL, "d and slots must be positive, total_tiles >= 0");
-    const int32_t rc = tree_args(max_bins, num_classes);
+    const int32_t rc = tree_args(max_bins, num_classes == 0 ? 2 : num_classes);   // (0: the regression table)
     if (rc) return rc;
     if (budget <= 0) budget = PSGD_TREE_SCRATCH_BUDGET;
     const psgd::TreeGeom gm = psgd::tree_geometry(d, max_bins, num_classes, slots, total_tiles, budget, 0);
     const int64_t v[PSGD_TREE_PLAN_LEN] = {gm.fchunk,   gm.sgroup,  gm.repl,      gm.lds_bytes, gm.n_groups, gm.scratch_bytes,
                                            gm.group_slots, gm.n_items, gm.span_rows, gm.pitch};
     std::memcpy(out, v, sizeof v);
+    return PSGD_OK;
+}
+
+// ---- Regression tree (kernels in psgd_tree.hip) ----
+// The label passes read the registry (score_prepare) like the binning; the others the caller's buffers alone.
+int32_t psgd_tree_label_range_device(psgd_ctx* ctx, const double* d_y, uint64_t* d_range, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_range) return fail(PSGD_EINVAL, "d_range is null");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int32_t rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const int P = (int)ctx->parts.size();
+    const int e = psgd::launch_tree_label_range(ctx->descs.as<psgd::ChainDesc>(), ctx->cidx.as<int64_t>() + P, P, d_y,
+                                                ctx->row_off.back(), d_range, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree label range launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_targets_device(psgd_ctx* ctx, const double* d_y, double ymin, int32_t s, uint32_t* d_q, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_q) return fail(PSGD_EINVAL, "d_q is null");
+    if (!(ymin - ymin == 0.0) || s < -1100 || s > 1100) return fail(PSGD_EINVAL, "ymin must be finite and |s| <= 1100");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int32_t rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);
+    if (rc) return rc;
+    ScoreScratchGuard guard{ctx, st};
+    const int P = (int)ctx->parts.size();
+    const int e = psgd::launch_tree_targets(ctx->descs.as<psgd::ChainDesc>(), ctx->cidx.as<int64_t>() + P, P, d_y,
+                                            ctx->row_off.back(), ymin, s, d_q, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree target launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_moments_device(psgd_ctx* ctx, const uint32_t* d_q, const int32_t* d_slot, int32_t slot0, int32_t n_slots,
+                                 int64_t* d_mom, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_q || !d_slot || !d_mom) return fail(PSGD_EINVAL, "d_q/d_slot/d_mom are null");
+    if (slot0 < 0 || n_slots < 1) return fail(PSGD_EINVAL, "slot0 must be >= 0 and n_slots >= 1");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    int32_t rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);   // (the row count is the registry's)
+    if (rc) return rc;
+    const int e = psgd::launch_tree_moments(d_q, d_slot, ctx->row_off.back(), slot0, n_slots, d_mom, ctx->num_cus, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("tree moments launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_histogram_reg_device(psgd_ctx* ctx, const uint8_t* d_bins, const uint32_t* d_q, const int32_t* d_slot,
+                                       int32_t max_bins, int32_t slot0, int32_t n_slots, int32_t replication,
+                                       int64_t* d_hist, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_bins || !d_q || !d_slot || !d_hist) return fail(PSGD_EINVAL, "d_bins/d_q/d_slot/d_hist are null");
+    int32_t rc = tree_args(max_bins, 2);
+    if (rc) return rc;
+    if (slot0 < 0 || n_slots < 1) return fail(PSGD_EINVAL, "slot0 must be >= 0 and n_slots >= 1");
+    if (replication < 0 || replication > 2) return fail(PSGD_EINVAL, "replication must be 0 (the plan's), 1 or 2");
+    if (!aligned16(d_bins)) return fail(PSGD_EINVAL, "d_bins must be 16-byte aligned");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    rc = tree_rows(ctx);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    rc = score_prepare(ctx, st);   // (the row count is the registry's)
+    if (rc) return rc;
+    const int64_t n_rows = ctx->row_off.back();
+    const psgd::TreeGeom gm = psgd::tree_geometry(ctx->parts.begin()->second.d, max_bins, 0, n_slots,
+                                                  (n_rows + psgd::kTreeTileRows - 1) / psgd::kTreeTileRows, INT64_MAX,
+                                                  replication);
+    const int e = psgd::launch_tree_hist_reg(d_bins, d_q, d_slot, n_rows, gm, slot0, n_slots, d_hist, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("regression histogram launch failed: ") + hipGetErrorString((hipError_t)e));
+    return PSGD_OK;
+}
+
+int32_t psgd_tree_best_split_reg_device(psgd_ctx* ctx, const int64_t* d_hist, const int64_t* d_mom,
+                                        const double* d_thresholds, const int32_t* d_nbins, int32_t d, int32_t max_bins,
+                                        int32_t n_slots, int32_t s, int64_t min_instances, double min_info_gain,
+                                        double* d_rec, void* stream) {
+    if (!ctx) return fail(PSGD_EINVAL, "ctx is null");
+    if (!d_hist || !d_mom || !d_thresholds || !d_nbins || !d_rec)
+        return fail(PSGD_EINVAL, "d_hist/d_mom/d_thresholds/d_nbins/d_rec are null");
+    const int32_t rc = tree_args(max_bins, 2);
+    if (rc) return rc;
+    if (d < 1 || n_slots < 1) return fail(PSGD_EINVAL, "d and n_slots must be positive");
+    if (s < -1100 || s > 1100) return fail(PSGD_EINVAL, "|s| must be <= 1100");
+    if (min_instances < 1 || !(min_info_gain >= 0.0))
+        return fail(PSGD_EINVAL, "min_instances must be >= 1 and min_info_gain >= 0");
+    DeviceGuard g(ctx->device);
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    const int e = psgd::launch_tree_best_split_reg(d_hist, d_mom, d_thresholds, d_nbins, d, max_bins, n_slots, s,
+                                                   min_instances, min_info_gain, d_rec, st);
+    if (e) return fail(PSGD_EDEVICE, std::string("regression split launch failed: ") + hipGetErrorString((hipError_t)e));
     return PSGD_OK;
 }
 

@@ -540,6 +540,8 @@ constexpr int kTreeMaxBins = 256;
 constexpr int kTreeMaxClasses = 32;
 constexpr int kTreeLdsCells = 16384;     // uint32 counters a workgroup of tree_hist keeps: 64 KiB, two workgroups a CU
 constexpr int kTreeTileRows = 256;       // rows a tile of the local row order
+constexpr int kTreeRegLdsCells = 5456;   // {uint32 count, 64-bit sum} cells of tree_hist_reg: 12 bytes each, 64 KiB at most
+constexpr int kTreeMomSlots = 1024;      // slots whose four 64-bit moments a workgroup of tree_moments keeps (32 KiB)
 struct TreeGeom {
     int32_t d, bins, classes;
     int32_t pitch;                 // bytes of a binned row: d rounded up to 16
@@ -574,6 +576,23 @@ int launch_tree_route(const uint8_t* bins, int pitch, int64_t n_rows, const int3
 // probability, feature (-1: a leaf), left, right, prediction}, checked by the caller.
 int launch_tree_predict(const ChainDesc* descs, const int64_t* row_off, int n_parts, int64_t n_rows, int storage,
                         const void* nodes, int n_nodes, int32_t* cls, double* prob, int num_cus, hipStream_t st);
+// Regression (tree_geometry with classes = 0 plans its histogram). Labels: the registered ones, or flat [n_rows]
+// when it is not null. range = {min key, max key, bad labels} over the finite labels (keys: the order-preserving
+// 64-bit image of a double; min > max without a finite label).
+int launch_tree_label_range(const ChainDesc* descs, const int64_t* row_off, int n_parts, const double* flat, int64_t n_rows,
+                            uint64_t* range, int num_cus, hipStream_t st);
+// q [n_rows] = rint((y - ymin) 2^s), 0 for a bad label.
+int launch_tree_targets(const ChainDesc* descs, const int64_t* row_off, int n_parts, const double* flat, int64_t n_rows,
+                        double ymin, int s, uint32_t* q, int num_cus, hipStream_t st);
+// mom [n_slots][4] (zeroed here) = {n, sum q, sum(q^2 >> 30), sum(q^2 & (2^30 - 1))} of slots slot0 .. .
+int launch_tree_moments(const uint32_t* q, const int32_t* slot, int64_t n_rows, int slot0, int n_slots, int64_t* mom,
+                        int num_cus, hipStream_t st);
+// hist [n_slots][d][bins][2] (zeroed here) = {rows, sum q} of the rows whose slot lies in [slot0, slot0 + n_slots).
+int launch_tree_hist_reg(const uint8_t* bins, const uint32_t* q, const int32_t* slot, int64_t n_rows, const TreeGeom& gm,
+                         int slot0, int n_slots, int64_t* hist, hipStream_t st);
+// rec [n_slots][4] = {feature (-1: a leaf), bin, threshold, gain} from hist and the slots' moments mom [n_slots][4].
+int launch_tree_best_split_reg(const int64_t* hist, const int64_t* mom, const double* thr, const int32_t* nbins, int d,
+                               int bins, int n_slots, int s, int64_t min_inst, double min_gain, double* rec, hipStream_t st);
 
 // ---- Random-forest classifier (psgd_forest.hip: psgd_forest_*) ----
 // The plan of a level's histogram pass over a frontier of `nodes` nodes with m subset features each: host

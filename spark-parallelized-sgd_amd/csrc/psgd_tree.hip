@@ -31,6 +31,10 @@
 //
 // tree_predict_dense: a lane a row, the node arrays in LDS while they fit 64 KiB (32 bytes a node), else
 // read through L2; at most `depth` scattered loads of the row's features.
+//
+// The regression tree (psgd_tree_label_range_device, psgd_tree_targets_device, psgd_tree_moments_device,
+// psgd_tree_histogram_reg_device, psgd_tree_best_split_reg_device) follows tree_predict_dense below: fixed-point
+// targets, node moments, a {count, sum} histogram and the variance split, each described at its kernel.
 #include <algorithm>
 
 #include "psgd_device.h"
@@ -367,6 +371,290 @@ __global__ __launch_bounds__(kTreeBlock) void tree_predict_dense(const ChainDesc
     }
 }
 
+// ---- regression: fixed-point targets, node moments, {count, sum} histograms, variance gains ----
+
+// The order-preserving 64-bit image of a double: a < b exactly when key(a) < key(b) as unsigned integers.
+__device__ __forceinline__ unsigned long long tree_key(double y) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(y);
+    return (u >> 63) ? ~u : (u | (1ull << 63));
+}
+__device__ __forceinline__ bool tree_finite(double y) {
+    return ((unsigned long long)__double_as_longlong(y) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
+}
+// Row `row`'s label: the registered one, or flat[row] when the caller passes labels of its own.
+__device__ __forceinline__ double tree_label(const ChainDesc* descs, const int64_t* row_off, int P, const double* flat,
+                                             int64_t row) {
+    if (flat) return flat[row];
+    const int p = tree_partition(row_off, P, row);
+    return descs[p].y[row - row_off[p]];
+}
+
+__global__ void tree_range_init(unsigned long long* range) {
+    range[0] = ~0ull;
+    range[1] = 0ull;
+    range[2] = 0ull;
+}
+
+// range = {min key, max key, labels that are NaN or infinite}: a lane a row, the wave by butterfly, the four
+// waves in LDS, then three integer atomics a workgroup -- integer min and max are exact in any order.
+__global__ __launch_bounds__(kTreeBlock) void tree_label_range(const ChainDesc* __restrict__ descs,
+                                                               const int64_t* __restrict__ row_off, int P,
+                                                               const double* __restrict__ flat, int64_t n_rows,
+                                                               unsigned long long* __restrict__ range) {
+    __shared__ unsigned long long part_s[kTreeWaves][3];
+    unsigned long long lo = ~0ull, hi = 0ull, bad = 0ull;
+    for (int64_t row = (int64_t)blockIdx.x * kTreeBlock + threadIdx.x; row < n_rows; row += (int64_t)gridDim.x * kTreeBlock) {
+        const double y = tree_label(descs, row_off, P, flat, row);
+        if (!tree_finite(y)) {
+            ++bad;
+            continue;
+        }
+        const unsigned long long k = tree_key(y);
+        lo = k < lo ? k : lo;
+        hi = k > hi ? k : hi;
+    }
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const unsigned long long l2 = __shfl_xor(lo, off), h2 = __shfl_xor(hi, off);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+        bad += __shfl_xor(bad, off);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        part_s[threadIdx.x >> 6][0] = lo;
+        part_s[threadIdx.x >> 6][1] = hi;
+        part_s[threadIdx.x >> 6][2] = bad;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kTreeWaves; ++w) {
+            lo = part_s[w][0] < lo ? part_s[w][0] : lo;
+            hi = part_s[w][1] > hi ? part_s[w][1] : hi;
+            bad += part_s[w][2];
+        }
+        if (lo <= hi) {
+            atomicMin(range, lo);
+            atomicMax(range + 1, hi);
+        }
+        if (bad) atomicAdd(range + 2, bad);
+    }
+}
+
+// q[row] = rint((y - ymin) 2^s): one rounded subtraction, an exact scaling, ties to even. 0 for a bad label.
+__global__ __launch_bounds__(kTreeBlock) void tree_targets(const ChainDesc* __restrict__ descs,
+                                                           const int64_t* __restrict__ row_off, int P,
+                                                           const double* __restrict__ flat, int64_t n_rows, double ymin,
+                                                           int s, uint32_t* __restrict__ q) {
+    for (int64_t row = (int64_t)blockIdx.x * kTreeBlock + threadIdx.x; row < n_rows; row += (int64_t)gridDim.x * kTreeBlock) {
+        const double y = tree_label(descs, row_off, P, flat, row);
+        const double t = tree_finite(y) ? rint(ldexp(y - ymin, s)) : 0.0;
+        q[row] = t >= 0.0 && t <= 1073741824.0 ? (uint32_t)t : 0u;
+    }
+}
+
+// The wave's sum of v (64-bit integers).
+__device__ __forceinline__ unsigned long long tree_wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// One slot's {n, S, sum(q^2 >> 30), sum(q^2 & (2^30 - 1))}, added into the workgroup's table in LDS.
+__device__ __forceinline__ void tree_mom_flush(unsigned long long* tab, int s, const unsigned long long (&a)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (a[k]) atomicAdd(tab + 4 * s + k, a[k]);
+}
+
+// mom [n_slots][4] (zeroed by the launch): blockIdx.x a span of rows, blockIdx.y a sub-group of kTreeMomSlots
+// slots. A lane keeps the four sums of its current slot in registers and adds them to the LDS table when its
+// slot changes. At the end a wave whose lanes all hold one slot (the root, a shallow level of sorted rows)
+// adds them up by butterfly and issues four LDS adds; any other wave's lanes add their own. One global
+// integer atomic a (workgroup, slot, member) that is not zero.
+__global__ __launch_bounds__(kTreeBlock) void tree_moments(const uint32_t* __restrict__ q, const int32_t* __restrict__ slot,
+                                                           int64_t n_rows, int64_t span_rows, int slot0, int n_slots,
+                                                           unsigned long long* __restrict__ mom) {
+    __shared__ unsigned long long mom_s[4 * kTreeMomSlots];
+    const int g0 = blockIdx.y * kTreeMomSlots;
+    const int sbase = slot0 + g0;
+    const int sn = min(kTreeMomSlots, n_slots - g0);
+    for (int i = threadIdx.x; i < 4 * sn; i += kTreeBlock) mom_s[i] = 0ull;
+    __syncthreads();
+    const int64_t r0 = (int64_t)blockIdx.x * span_rows;
+    const int64_t r1 = min(r0 + span_rows, n_rows);
+    int cur = -1;
+    unsigned long long a[4] = {0ull, 0ull, 0ull, 0ull};
+    for (int64_t row = r0 + threadIdx.x; row < r1; row += kTreeBlock) {
+        const int s = slot[row] - sbase;
+        if (s < 0 || s >= sn) continue;
+        if (s != cur) {
+            if (cur >= 0) tree_mom_flush(mom_s, cur, a);
+            cur = s;
+            a[0] = a[1] = a[2] = a[3] = 0ull;
+        }
+        const unsigned long long t = q[row], t2 = t * t;   // (t <= 2^30: t2 <= 2^60)
+        a[0] += 1ull;
+        a[1] += t;
+        a[2] += t2 >> 30;
+        a[3] += t2 & ((1ull << 30) - 1ull);
+    }
+    const int first = __shfl(cur, 0);
+    if (__all(cur == first)) {
+        if (first >= 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a[k] = tree_wave_sum(a[k]);
+            if ((threadIdx.x & 63) == 0) tree_mom_flush(mom_s, first, a);
+        }
+    } else if (cur >= 0) {
+        tree_mom_flush(mom_s, cur, a);
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * sn; i += kTreeBlock) {
+        const unsigned long long v = mom_s[i];
+        if (v) atomicAdd(mom + 4 * (int64_t)g0 + i, v);
+    }
+}
+
+// tree_hist's work split, row reads and part-vector chunks with a cell of {uint32 count, 64-bit sum of the
+// rows' targets}: the sums [copy][slot][feature][bin] first in LDS, the counts after them (12 bytes a cell,
+// gm.repl cells <= kTreeRegLdsCells). A lane issues one 32-bit and one native 64-bit LDS integer add a
+// feature: eight targets near 2^30 already pass a uint32. hist [n_slots][d][bins][2] = {count, sum}.
+__global__ __launch_bounds__(kTreeBlock, 2) void tree_hist_reg(const uint8_t* __restrict__ bins,
+                                                               const uint32_t* __restrict__ q,
+                                                               const int32_t* __restrict__ slot, int64_t n_rows,
+                                                               TreeGeom gm, int slot0, int n_slots,
+                                                               unsigned long long* __restrict__ hist) {
+    extern __shared__ unsigned long long tree_sum[];
+    const int B = gm.bins, FC = gm.fchunk, S = gm.sgroup, d = gm.d;
+    const int cells = S * FC * B;                        // one copy
+    unsigned* tree_cnt = reinterpret_cast<unsigned*>(tree_sum + cells * gm.repl);
+    int64_t item = blockIdx.x;
+    const int fc = (int)(item % gm.n_fchunks);
+    item /= gm.n_fchunks;
+    const int sg = (int)(item % gm.n_sgroups);
+    const int64_t span = item / gm.n_sgroups;
+    for (int i = threadIdx.x; i < cells * gm.repl; i += kTreeBlock) {
+        tree_sum[i] = 0ull;
+        tree_cnt[i] = 0u;
+    }
+    __syncthreads();
+    const int nvec = gm.pitch >> 4;
+    const bool wide = FC >= 16;
+    const int vec0 = wide ? fc * (FC >> 4) : (fc * FC) >> 4;
+    const int nv = wide ? min(FC >> 4, nvec - vec0) : 1;
+    const int e_lo = wide ? 0 : (fc * FC) & 15, e_hi = wide ? 16 : e_lo + FC;
+    const int rps = kTreeBlock / nv;
+    const int rin = threadIdx.x / nv, v = threadIdx.x - rin * nv;
+    const int sbase = slot0 + sg * S;
+    const int sn = min(S, n_slots - sg * S);
+    const int64_t r0 = span * gm.span_rows;
+    const int64_t r1 = min(r0 + gm.span_rows, n_rows);
+    if (rin < rps) {
+        for (int64_t row = r0 + rin; row < r1; row += rps) {
+            const int s = slot[row] - sbase;
+            if (s < 0 || s >= sn) continue;
+            const unsigned long long t = q[row];
+            const uint4 w4 = *reinterpret_cast<const uint4*>(bins + row * gm.pitch + 16 * (vec0 + v));
+            const unsigned w[4] = {w4.x, w4.y, w4.z, w4.w};
+            const int base = (gm.repl == 2 && (row & 1) ? cells : 0) + s * FC * B;
+            const int fl0 = 16 * (vec0 + v) - fc * FC;   // the vector's byte 0 as a feature of the chunk
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int b = (int)((w[e >> 2] >> (8 * (e & 3))) & 255u);
+                const int fl = fl0 + e;
+                if (e >= e_lo && e < e_hi && fc * FC + fl < d && b < B) {
+                    atomicAdd(tree_cnt + base + fl * B + b, 1u);
+                    atomicAdd(tree_sum + base + fl * B + b, t);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < cells; i += kTreeBlock) {
+        const unsigned c = tree_cnt[i] + (gm.repl == 2 ? tree_cnt[cells + i] : 0u);
+        if (!c) continue;
+        const unsigned long long sum = tree_sum[i] + (gm.repl == 2 ? tree_sum[cells + i] : 0ull);
+        const int s = i / (FC * B);
+        const int rem = i - s * FC * B;
+        const int fl = rem / B;
+        const int f = fc * FC + fl, gs = sg * S + s;
+        if (f < d && gs < n_slots) {
+            unsigned long long* cell = hist + 2 * (((int64_t)gs * d + f) * B + (rem - fl * B));
+            atomicAdd(cell, (unsigned long long)c);
+            if (sum) atomicAdd(cell + 1, sum);
+        }
+    }
+}
+
+// rec [n_slots][4] = {feature (-1: a leaf), bin, threshold, gain}. The slot's n and S come from its moments;
+// a wave takes a feature, lane j bins j, j + 64, ..: exact inclusive scans of the counts and of the sums,
+// carried from 64 bins to the next in registers, give nL and SL, and nR = n - nL, SR = S - SL as integers.
+// gain = ((SL^2 / nL + SR^2 / nR - S^2 / n) / n) 2^-2s in fp64; the candidates, the validity and the tie rule
+// are tree_best_split's.
+__global__ __launch_bounds__(kTreeBlock) void tree_best_split_reg(const unsigned long long* __restrict__ hist,
+                                                                  const long long* __restrict__ mom,
+                                                                  const double* __restrict__ thr,
+                                                                  const int32_t* __restrict__ nbins, int d, int B, int s,
+                                                                  long long min_inst, double min_gain,
+                                                                  double* __restrict__ rec) {
+    __shared__ TreeBest best_s[kTreeWaves];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int slot = blockIdx.x;
+    const unsigned long long* H = hist + (int64_t)slot * d * B * 2;
+    const long long n = mom[4 * (int64_t)slot], S = mom[4 * (int64_t)slot + 1];
+    const double dn = (double)n;
+    const double parent = ((double)S * (double)S) / dn;
+    double bg = 0.0;
+    int bf = -1, bb = -1;
+    for (int f = wave; f < d; f += kTreeWaves) {
+        int ncand = nbins[f] - 1;                        // candidates: bins 0 .. nb_f - 2
+        ncand = ncand > B - 1 ? B - 1 : ncand;
+        const unsigned long long* Hf = H + (int64_t)f * B * 2;
+        unsigned long long cn = 0ull, cs = 0ull;
+        for (int b0 = 0; b0 < ncand; b0 += 64) {         // (uniform over the wave)
+            const int b = b0 + lane;
+            const unsigned long long hn = tree_scan(b < ncand ? Hf[2 * b] : 0ull, lane);
+            const unsigned long long hs = tree_scan(b < ncand ? Hf[2 * b + 1] : 0ull, lane);
+            const long long nL = (long long)(cn + hn), SL = (long long)(cs + hs);
+            const long long nR = n - nL, SR = S - SL;
+            if (b < ncand && nL >= min_inst && nR >= min_inst && nL > 0 && nR > 0) {
+                const double dl = (double)SL, dr = (double)SR;
+                const double gain = ldexp(((dl * dl) / (double)nL + (dr * dr) / (double)nR - parent) / dn, -2 * s);
+                if (bf < 0 || gain > bg) {
+                    bg = gain;
+                    bf = f;
+                    bb = b;
+                }
+            }
+            cn += __shfl(hn, 63);
+            cs += __shfl(hs, 63);
+        }
+    }
+    for (int off = 1; off < 64; off <<= 1) {
+        const double pg = __shfl_xor(bg, off);
+        const int pf = __shfl_xor(bf, off), pb = __shfl_xor(bb, off);
+        if (tree_better(pg, pf, pb, bg, bf, bb)) {
+            bg = pg;
+            bf = pf;
+            bb = pb;
+        }
+    }
+    if (lane == 0) best_s[wave] = TreeBest{bg, bf, bb};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        TreeBest w = best_s[0];
+        for (int i = 1; i < kTreeWaves; ++i)
+            if (tree_better(best_s[i].gain, best_s[i].f, best_s[i].b, w.gain, w.f, w.b)) w = best_s[i];
+        const bool split = w.f >= 0 && w.gain > 0.0 && w.gain >= min_gain;
+        double* out = rec + 4 * (int64_t)slot;
+        out[0] = split ? (double)w.f : -1.0;
+        out[1] = split ? (double)w.b : -1.0;
+        out[2] = split ? thr[(int64_t)w.f * (B - 1) + w.b] : 0.0;
+        out[3] = w.f >= 0 ? w.gain : 0.0;
+    }
+}
+
 unsigned tree_blocks(int64_t n, int per, int num_cus) {
     return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, (int64_t)num_cus * 8));
 }
@@ -381,14 +669,17 @@ TreeGeom tree_geometry(int d, int bins, int classes, int slots, int64_t n_tiles,
     gm.pitch = 16 * ((d + 15) / 16);
     const int nvec = gm.pitch / 16;
     // the frontier in groups whose 64-bit tables fit the budget
-    const int64_t per_slot = (int64_t)d * bins * classes * (int64_t)sizeof(int64_t);
+    // (classes 0: the regression table, a cell {count, sum} of 2 x 64 bits, 12 bytes in LDS)
+    const bool reg = classes == 0;
+    const int64_t per_slot = (int64_t)d * bins * (reg ? 2 : classes) * (int64_t)sizeof(int64_t);
     gm.group_slots = (int32_t)std::max<int64_t>(1, std::min<int64_t>(slots, budget / per_slot));
     gm.n_groups = (slots + gm.group_slots - 1) / gm.group_slots;
     gm.scratch_bytes = gm.group_slots * per_slot;
     // the sub-table of an item: whole vectors of 16 features first, then slots, then a second copy
     // when one is asked for (repl 2) or comes free (repl 0: every feature and slot of the group fit twice)
-    const int cells_f = bins * classes;
-    const int cap = repl == 2 ? kTreeLdsCells / 2 : kTreeLdsCells;
+    const int cells_f = reg ? bins : bins * classes;
+    const int lds_cells = reg ? kTreeRegLdsCells : kTreeLdsCells;
+    const int cap = repl == 2 ? lds_cells / 2 : lds_cells;
     if (16 * cells_f <= cap) {
         const int units = cap / (16 * cells_f);
         const int fv = std::min(units, nvec);
@@ -401,8 +692,8 @@ TreeGeom tree_geometry(int d, int bins, int classes, int slots, int64_t n_tiles,
         gm.sgroup = 1;
     }
     const int64_t one = (int64_t)gm.sgroup * gm.fchunk * cells_f;
-    gm.repl = repl == 2 || (repl == 0 && 2 * one <= kTreeLdsCells) ? 2 : 1;
-    gm.lds_bytes = gm.repl * one * (int64_t)sizeof(uint32_t);
+    gm.repl = repl == 2 || (repl == 0 && 2 * one <= lds_cells) ? 2 : 1;
+    gm.lds_bytes = gm.repl * one * (int64_t)(reg ? sizeof(uint32_t) + sizeof(uint64_t) : sizeof(uint32_t));
     gm.n_fchunks = gm.fchunk >= 16 ? (nvec + gm.fchunk / 16 - 1) / (gm.fchunk / 16) : (d + gm.fchunk - 1) / gm.fchunk;
     gm.n_sgroups = (gm.group_slots + gm.sgroup - 1) / gm.sgroup;
     const int64_t sub = (int64_t)gm.n_fchunks * gm.n_sgroups;
@@ -491,6 +782,67 @@ int launch_tree_predict(const ChainDesc* descs, const int64_t* row_off, int n_pa
         if (lds) hipLaunchKernelGGL((tree_predict_dense<double, true>), grid, block, 0, st, descs, row_off, n_parts, n_rows, nd, n_nodes, cls, prob);
         else hipLaunchKernelGGL((tree_predict_dense<double, false>), grid, block, 0, st, descs, row_off, n_parts, n_rows, nd, n_nodes, cls, prob);
     }
+    return (int)hipGetLastError();
+}
+
+int launch_tree_label_range(const ChainDesc* descs, const int64_t* row_off, int n_parts, const double* flat, int64_t n_rows,
+                            uint64_t* range, int num_cus, hipStream_t st) {
+    unsigned long long* R = reinterpret_cast<unsigned long long*>(range);
+    hipLaunchKernelGGL(tree_range_init, dim3(1), dim3(1), 0, st, R);
+    int e = (int)hipGetLastError();
+    if (e || n_rows <= 0) return e;
+    hipLaunchKernelGGL(tree_label_range, dim3(tree_blocks(n_rows, kTreeBlock, num_cus)), dim3(kTreeBlock), 0, st, descs,
+                       row_off, n_parts, flat, n_rows, R);
+    return (int)hipGetLastError();
+}
+
+int launch_tree_targets(const ChainDesc* descs, const int64_t* row_off, int n_parts, const double* flat, int64_t n_rows,
+                        double ymin, int s, uint32_t* q, int num_cus, hipStream_t st) {
+    if (n_rows <= 0) return 0;
+    hipLaunchKernelGGL(tree_targets, dim3(tree_blocks(n_rows, kTreeBlock, num_cus)), dim3(kTreeBlock), 0, st, descs, row_off,
+                       n_parts, flat, n_rows, ymin, s, q);
+    return (int)hipGetLastError();
+}
+
+int launch_tree_moments(const uint32_t* q, const int32_t* slot, int64_t n_rows, int slot0, int n_slots, int64_t* mom,
+                        int num_cus, hipStream_t st) {
+    unsigned long long* M = reinterpret_cast<unsigned long long*>(mom);
+    const int64_t total = 4 * (int64_t)n_slots;
+    hipLaunchKernelGGL(tree_zero, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 2048))),
+                       dim3(256), 0, st, M, total);
+    int e = (int)hipGetLastError();
+    if (e || n_rows <= 0) return e;
+    // spans of whole tiles, about four a CU; every sub-group of kTreeMomSlots slots reads the spans again
+    const int64_t T = (n_rows + kTreeTileRows - 1) / kTreeTileRows;
+    const int64_t want = std::min<int64_t>(T, (int64_t)num_cus * 4);
+    const int64_t span_tiles = (T + want - 1) / want;
+    const dim3 grid((unsigned)((T + span_tiles - 1) / span_tiles), (unsigned)((n_slots + kTreeMomSlots - 1) / kTreeMomSlots));
+    hipLaunchKernelGGL(tree_moments, grid, dim3(kTreeBlock), 0, st, q, slot, n_rows, span_tiles * kTreeTileRows, slot0,
+                       n_slots, M);
+    return (int)hipGetLastError();
+}
+
+int launch_tree_hist_reg(const uint8_t* bins, const uint32_t* q, const int32_t* slot, int64_t n_rows, const TreeGeom& gm,
+                         int slot0, int n_slots, int64_t* hist, hipStream_t st) {
+    unsigned long long* H = reinterpret_cast<unsigned long long*>(hist);
+    const int64_t total = (int64_t)n_slots * gm.d * gm.bins * 2;
+    hipLaunchKernelGGL(tree_zero, dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 2048))),
+                       dim3(256), 0, st, H, total);
+    int e = (int)hipGetLastError();
+    if (e || n_rows <= 0) return e;
+    TreeGeom g = gm;
+    g.n_sgroups = (n_slots + gm.sgroup - 1) / gm.sgroup;   // (a last group may be short)
+    const int64_t items = g.n_spans * g.n_fchunks * g.n_sgroups;
+    hipLaunchKernelGGL(tree_hist_reg, dim3((unsigned)items), dim3(kTreeBlock), (size_t)g.lds_bytes, st, bins, q, slot, n_rows,
+                       g, slot0, n_slots, H);
+    return (int)hipGetLastError();
+}
+
+int launch_tree_best_split_reg(const int64_t* hist, const int64_t* mom, const double* thr, const int32_t* nbins, int d,
+                               int bins, int n_slots, int s, int64_t min_inst, double min_gain, double* rec, hipStream_t st) {
+    hipLaunchKernelGGL(tree_best_split_reg, dim3((unsigned)n_slots), dim3(kTreeBlock), 0, st,
+                       reinterpret_cast<const unsigned long long*>(hist), reinterpret_cast<const long long*>(mom), thr, nbins,
+                       d, bins, s, (long long)min_inst, min_gain, rec);
     return (int)hipGetLastError();
 }
 

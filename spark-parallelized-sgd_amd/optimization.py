@@ -1033,6 +1033,106 @@ class HipEngine(ShardedEngine):
             return cls[:n], None if prob is None else prob[:n]
         return self._tree_run(call)
 
+    # regression tree (psgd_tree_*_reg_device and the target passes; tree.py) -----------------------
+    def _tree_allreduce(self, buf, op=None):
+        """`buf` summed (or combined by `op`) over the ranks; through the host under gloo, which takes CPU tensors."""
+        if self.world == 1:
+            return buf
+        import torch.distributed as dist
+        kw = {} if op is None else {"op": op}
+        if dist.get_backend() == "gloo":
+            h = buf.cpu()
+            dist.all_reduce(h, **kw)
+            return h.to(self.dev)
+        dist.all_reduce(buf, **kw)
+        return buf
+
+    def tree_targets(self, labels=None):
+        """The fixed-point targets of this rank's rows (include/psgd.h has the definition): a tree.TreeTargets of
+        q (uint32 viewed as int32 [local_rows()], engine-owned, on the device), ymin and s, the range taken
+        over all ranks. labels: a device float64 tensor of local_rows() values to use in place of the
+        registered labels. A NaN or infinite label raises."""
+        from .tree import TreeTargets, target_scale
+        torch = self.torch
+        n = self.local_rows()
+        if labels is not None and (labels.dtype != torch.float64 or labels.numel() != n or not labels.is_contiguous()):
+            raise IllegalArgumentException(f"requirement failed: labels must be {n} contiguous float64 values on the device")
+        y_ptr = 0 if labels is None else labels.data_ptr()
+
+        def call_range(run):
+            rng = torch.zeros(3, dtype=torch.int64, device=self.dev)
+            if run:
+                self.ctx.tree_label_range_device(y_ptr, rng.data_ptr(), self.stream.cuda_stream)
+            return rng
+        key = self._tree_run(call_range).cpu().numpy().view(np.uint64)
+        run = self.n_local > 0 and key[0] <= key[1]
+        bits = np.where(key[:2] >> np.uint64(63), key[:2] ^ np.uint64(1 << 63), ~key[:2])
+        ext = torch.from_numpy(np.array([-bits.view(np.float64)[0], bits.view(np.float64)[1]] if run else [-np.inf, -np.inf]))
+        bad = torch.tensor([int(key[2]) if self.n_local > 0 else 0], dtype=torch.int64)
+        if self.world > 1:
+            import torch.distributed as dist
+            ext = self._tree_allreduce(ext.to(self.dev), dist.ReduceOp.MAX).cpu()   # {-ymin, ymax}: one max
+            bad = self._tree_allreduce(bad.to(self.dev)).cpu()
+        if int(bad[0]) > 0:
+            raise IllegalArgumentException(f"requirement failed: {int(bad[0])} labels are NaN or infinite")
+        ymin, ymax = -float(ext[0]) + 0.0, float(ext[1]) + 0.0
+        if not np.isfinite(ymax - ymin):
+            raise IllegalArgumentException("requirement failed: the data has no finite label, or the labels' range overflows")
+        s = target_scale(ymin, ymax)
+
+        def call(run):
+            q = torch.zeros(max(n, 1), dtype=torch.int32, device=self.dev)
+            if run:
+                self.ctx.tree_targets_device(y_ptr, ymin, s, q.data_ptr(), self.stream.cuda_stream)
+            return q
+        return TreeTargets(self._tree_run(call)[:n], ymin, s)
+
+    def tree_moments(self, targets, slots, n_slots: int = 1):
+        """{n, sum q, sum(q^2 >> 30), sum(q^2 & (2^30 - 1))} of slots 0 .. n_slots - 1 over every row of the data,
+        on all ranks: a device int64 tensor [n_slots, 4] (psgd_tree_moments_device)."""
+        torch = self.torch
+
+        def call(run):
+            mom = torch.zeros((int(n_slots), 4), dtype=torch.int64, device=self.dev)
+            if run:
+                self.ctx.tree_moments_device(targets.q.data_ptr(), slots.data_ptr(), 0, n_slots, mom.data_ptr(),
+                                             self.stream.cuda_stream)
+            return self._tree_allreduce(mom)
+        return self._tree_run(call)
+
+    def tree_histogram_reg(self, bins, targets, slots, group=None, replication: int = 0):
+        """The regression form of tree_histogram: H[slot][f][b] = {rows, sum q} of the slots `group`, a device
+        int64 tensor [slots, d, maxBins, 2] added over the ranks (psgd_tree_histogram_reg_device)."""
+        torch = self.torch
+        slot0, n_slots = (0, 1) if group is None else (int(group[0]), int(group[1]))
+        nf, B = self._data.num_features, bins.max_bins
+
+        def call(run):
+            hist = torch.zeros((n_slots, nf, B, 2), dtype=torch.int64, device=self.dev)
+            if run:
+                self.ctx.tree_histogram_reg_device(bins.bins.data_ptr(), targets.q.data_ptr(), slots.data_ptr(), B, slot0,
+                                                   n_slots, replication, hist.data_ptr(), self.stream.cuda_stream)
+            return self._tree_allreduce(hist)
+        return self._tree_run(call)
+
+    def tree_best_split_reg(self, hist, moments, bins, targets, minInstancesPerNode: int = 1, minInfoGain: float = 0.0):
+        """The regression form of tree_best_split: one record {feature (-1: a leaf), bin, threshold, gain} a slot
+        of `hist` [slots, d, maxBins, 2], a device tensor [slots, 4] of doubles; `moments` [slots, 4] are those
+        slots' rows of tree_moments' table (psgd_tree_best_split_reg_device)."""
+        torch = self.torch
+        n_slots, nf, B, _ = (int(v) for v in hist.shape)
+        mom = moments.contiguous()
+        if tuple(mom.shape) != (n_slots, 4) or mom.dtype != torch.int64:
+            raise IllegalArgumentException(f"requirement failed: moments must be int64 [{n_slots}, 4]")
+
+        def call(_run):
+            rec = torch.zeros((n_slots, 4), dtype=torch.float64, device=self.dev)
+            self.ctx.tree_best_split_reg_device(hist.data_ptr(), mom.data_ptr(), bins.thresholds.data_ptr(),
+                                                bins.nbins.data_ptr(), nf, B, n_slots, targets.s, minInstancesPerNode,
+                                                minInfoGain, rec.data_ptr(), self.stream.cuda_stream)
+            return rec
+        return self._tree_run(call, rows=False)
+
     # random forest (psgd_forest_*_device; tree.py) -------------------------------------------------
     def _forest_row0(self) -> int:
         """The global index of this rank's first row: the rows of the partitions before its own."""

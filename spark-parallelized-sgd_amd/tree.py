@@ -16,7 +16,17 @@ table exceeds scratchBudget bytes is processed in groups of slots (psgd_tree_pla
 
 The row sample of find_splits is this project's convention, as in KMeans: every row while n <=
 max(maxBins^2, 10,000), else that many distinct positions from numpy.random.default_rng(seed), read as the
-engine registered them. Regression trees and categorical features are not built.
+engine registered them. Categorical features are not built.
+
+DecisionTree.trainRegressor(data, maxDepth=5, maxBins=32) trains a variance tree over the same binned rows.
+The labels become fixed-point targets once (HipEngine.tree_targets: q = rint((y - ymin) 2^s) below 2^30, 4 bytes
+a row on the device; include/psgd.h has the definition), and a level is the node moments of every open node
+(tree_moments: n, sum q and sum q^2 as integers), then, for the nodes that may split, the {count, sum}
+histogram and the variance split (tree_histogram_reg, tree_best_split_reg) and the routing pass. The host
+forms a node's value ymin + S / (n 2^s) and its variance from the integers as exact rationals, rounded once;
+a node at maxDepth, of variance exactly 0 or of fewer than 2 minInstancesPerNode rows is a leaf and gets no
+histogram pass (one routing pass closes up the slots of the others). Every child of a split gets a slot. The
+model's algo is "Regression", its prediction float64, its counts replaced by n; predict gives float64 tensors.
 
 RandomForest.trainClassifier trains numTrees such trees on bagged rows, each node looking at a random subset
 of the features (include/psgd.h has the bag weight; forest_cut, forest_subset_size and forest_subset are the
@@ -49,6 +59,19 @@ class TreeBins(NamedTuple):
     thresholds: object    # f64 [d, maxBins - 1] on the device
     nbins: object         # int32 [d] on the device
     max_bins: int
+
+
+class TreeTargets(NamedTuple):
+    """HipEngine.tree_targets' result: the rows' fixed-point regression targets and their unit."""
+    q: object             # int32 [local rows] on the device: rint((y - ymin) 2^s), 0 .. 2^30
+    ymin: float           # the smallest label over all ranks
+    s: int                # a target's unit is 2^-s
+
+
+def target_scale(ymin: float, ymax: float) -> int:
+    """The largest integer s with (ymax - ymin) 2^s < 2^30, the difference as fp64 rounds it; 0 for a constant label."""
+    r = float(ymax) - float(ymin)
+    return 30 - math.frexp(r)[1] if r > 0.0 else 0       # r = m 2^e with 1/2 <= m < 1: m 2^30 < 2^30 <= m 2^31
 
 
 def _engine_for(data: PartitionedData, engine):
@@ -118,10 +141,12 @@ def _impurity(counts: np.ndarray, kind: str) -> float:
 class DecisionTreeModel:
     """A trained classifier as arrays, node 0 the root and a node's children after it: id (MLlib's), feature
     (-1: a leaf), threshold, left, right (indices into the arrays), prediction, probability, gain, impurity
-    and counts [numNodes, numClasses]."""
+    and counts [numNodes, numClasses]. A regression model (algo "Regression", numClasses 0) has a float64
+    prediction, the same values in probability (the member the prediction kernel writes out), and the nodes' row
+    counts n in place of counts."""
 
-    def __init__(self, nodes: dict, numClasses: int, numFeatures: int):
-        self.nodes, self.numClasses, self.numFeatures = nodes, int(numClasses), int(numFeatures)
+    def __init__(self, nodes: dict, numClasses: int, numFeatures: int, algo: str = "Classification"):
+        self.nodes, self.numClasses, self.numFeatures, self.algo = nodes, int(numClasses), int(numFeatures), algo
         for key, value in nodes.items():
             setattr(self, key, value)
 
@@ -135,13 +160,17 @@ class DecisionTreeModel:
 
     def predict(self, data: PartitionedData, *, engine=None):
         """The predicted class of every row: one device int32 tensor per partition of `data` (empty for another
-        rank's partitions)."""
+        rank's partitions). A regression model gives float64 tensors of the leaves' values."""
         if data.num_features != self.numFeatures:
             raise IllegalArgumentException(
                 f"requirement failed: vector sizes do not match: Expected {self.numFeatures} but found {data.num_features}")
         _check_dense(data)
         engine = _engine_for(data, engine)
-        cls, _ = engine.tree_predict(self.nodes)
+        if self.algo == "Regression":
+            nodes = dict(self.nodes, prediction=np.zeros(self.numNodes, dtype=np.int32))
+            cls = engine.tree_predict(nodes, probability=True)[1]
+        else:
+            cls, _ = engine.tree_predict(self.nodes)
         out, at = [], 0
         for p, part in enumerate(data.partitions):
             n = part.n_rows if engine.lo <= p < engine.hi else 0
@@ -150,7 +179,8 @@ class DecisionTreeModel:
         return out
 
     def toDebugString(self) -> str:
-        lines = [f"DecisionTreeModel classifier of depth {self.depth} with {self.numNodes} nodes"]
+        kind = "regressor" if self.algo == "Regression" else "classifier"
+        lines = [f"DecisionTreeModel {kind} of depth {self.depth} with {self.numNodes} nodes"]
 
         def walk(i: int, indent: int):
             pad = " " * indent
@@ -167,19 +197,23 @@ class DecisionTreeModel:
 
 
 def _check_train_args(data, numClasses, categoricalFeaturesInfo, impurity, maxDepth, maxBins, minInstancesPerNode,
-                      minInfoGain):
-    """trainClassifier's refusals, the tree's and the forest's alike."""
+                      minInfoGain, regression=False):
+    """trainClassifier's refusals, the tree's and the forest's alike; regression: trainRegressor's (no classes)."""
     if categoricalFeaturesInfo:
         raise UnsupportedOperationException("categorical features are not built: categoricalFeaturesInfo must be empty")
-    if impurity == "variance":
-        raise UnsupportedOperationException("regression trees are not built: impurity is 'gini' or 'entropy'")
-    if impurity not in TREE_IMPURITIES:
-        raise IllegalArgumentException(f"requirement failed: unknown impurity {impurity!r}")
     K = numClasses
-    if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 2:
-        raise IllegalArgumentException(f"requirement failed: numClasses must be an integer >= 2 (got {K!r})")
-    if K > TREE_MAX_CLASSES:
-        raise UnsupportedOperationException(f"a tree takes at most {TREE_MAX_CLASSES} classes (got {K})")
+    if regression:
+        if impurity != "variance":
+            raise IllegalArgumentException(f"requirement failed: a regression tree's impurity is 'variance' (got {impurity!r})")
+    else:
+        if impurity == "variance":
+            raise UnsupportedOperationException("a classifier's impurity is 'gini' or 'entropy': 'variance' is trainRegressor's")
+        if impurity not in TREE_IMPURITIES:
+            raise IllegalArgumentException(f"requirement failed: unknown impurity {impurity!r}")
+        if isinstance(K, (bool, np.bool_)) or not isinstance(K, (int, np.integer)) or K < 2:
+            raise IllegalArgumentException(f"requirement failed: numClasses must be an integer >= 2 (got {K!r})")
+        if K > TREE_MAX_CLASSES:
+            raise UnsupportedOperationException(f"a tree takes at most {TREE_MAX_CLASSES} classes (got {K})")
     if isinstance(maxDepth, (bool, np.bool_)) or int(maxDepth) < 0:
         raise IllegalArgumentException(f"requirement failed: maxDepth must be nonnegative but got {maxDepth!r}")
     if int(maxDepth) > 30:
@@ -244,6 +278,97 @@ class DecisionTree:
                 engine.tree_route(bins, slots, table)
             frontier, level = nxt, level + 1
         return DecisionTreeModel(_node_arrays(done, K), K, d)
+
+    @staticmethod
+    def trainRegressor(data: PartitionedData, categoricalFeaturesInfo=None, impurity: str = "variance", maxDepth: int = 5,
+                       maxBins: int = 32, minInstancesPerNode: int = 1, minInfoGain: float = 0.0, seed=None, *, engine=None,
+                       scratchBudget: int = 0) -> DecisionTreeModel:
+        """A level is the node moments of every open node, then the {count, sum} histogram and the variance split
+        of those that may split (the module docstring has the loop)."""
+        _check_train_args(data, 0, categoricalFeaturesInfo, impurity, maxDepth, maxBins, minInstancesPerNode, minInfoGain,
+                          regression=True)
+        maxDepth, maxBins, minInst = int(maxDepth), int(maxBins), int(minInstancesPerNode)
+        counts = getattr(data, "partition_counts", None)
+        if (int(np.sum(counts)) if counts is not None else data.count()) >= 1 << 33:
+            raise UnsupportedOperationException("a regression tree takes fewer than 2^33 rows: its 64-bit sums must stay below 2^63")
+        engine = _engine_for(data, engine)
+        thr, nbins = find_splits(data, maxBins, seed, engine=engine)
+        bins = engine.tree_bin(thr, nbins)
+        targets = engine.tree_targets()
+        slots = engine.tree_slots()
+        d = data.num_features
+        done = {}                       # MLlib id -> the node's fields
+        frontier = [1]                  # the open nodes' ids, in slot order
+        level = 0
+        while frontier:
+            mom_dev = engine.tree_moments(targets, slots, len(frontier))
+            mom = mom_dev.cpu().numpy()
+            keep = []                   # the slots that may split
+            for s, nid in enumerate(frontier):
+                n, S, S2 = int(mom[s, 0]), int(mom[s, 1]), (int(mom[s, 2]) << 30) + int(mom[s, 3])
+                done[nid] = dict(_regression_stats(n, S, S2, targets.ymin, targets.s), feature=-1, bin=-1, threshold=0.0,
+                                 gain=0.0)
+                if level < maxDepth and n * S2 != S * S and n >= 2 * minInst:
+                    keep.append(s)
+            if not keep:
+                break
+            if len(keep) < len(frontier):   # the leaves' rows leave, the others' slots close up: one routing pass
+                table = np.full((len(frontier), 4), -1, dtype=np.int32)
+                for new, s in enumerate(keep):
+                    table[s] = (0, 255, new, new)       # (every bin is <= 255: "left")
+                engine.tree_route(bins, slots, table)
+                frontier = [frontier[s] for s in keep]
+                mom_dev = mom_dev[keep]
+            A = len(frontier)
+            plan = tree_plan("f32", d, maxBins, 0, A, 0, scratchBudget)
+            recs = []
+            for s0 in range(0, A, plan["group_slots"]):
+                g = min(plan["group_slots"], A - s0)
+                hist = engine.tree_histogram_reg(bins, targets, slots, (s0, g))
+                recs.append(engine.tree_best_split_reg(hist, mom_dev[s0: s0 + g], bins, targets, minInst, minInfoGain).cpu().numpy())
+            rec = np.concatenate(recs)
+            table = np.full((A, 4), -1, dtype=np.int32)
+            nxt = []
+            for s, nid in enumerate(frontier):
+                r = rec[s]
+                if r[0] < 0:
+                    continue
+                done[nid].update(feature=int(r[0]), bin=int(r[1]), threshold=float(r[2]), gain=float(r[3]))
+                table[s] = (int(r[0]), int(r[1]), len(nxt), len(nxt) + 1)    # both children get slots
+                nxt += [2 * nid, 2 * nid + 1]
+            if nxt:
+                engine.tree_route(bins, slots, table)
+            frontier, level = nxt, level + 1
+        return DecisionTreeModel(_regression_arrays(done), 0, d, "Regression")
+
+
+def _regression_stats(n: int, S: int, S2: int, ymin: float, s: int) -> dict:
+    """A node's value ymin + S / (n 2^s) and variance (n S2 - S^2) / (n 2^s)^2 from its integer moments: exact
+    rationals, each rounded once."""
+    from fractions import Fraction
+    if n == 0:
+        return dict(n=0, prediction=float(ymin), impurity=0.0)
+    unit = Fraction(1 << s) if s >= 0 else Fraction(1, 1 << -s)
+    return dict(n=n, prediction=float(Fraction(ymin) + Fraction(S, n) / unit),
+                impurity=float(Fraction(n * S2 - S * S, n * n) / (unit * unit)))
+
+
+def _regression_arrays(done: dict) -> dict:
+    ids = sorted(done)                  # MLlib ids ascend level by level: a child lies after its parent
+    at = {nid: i for i, nid in enumerate(ids)}
+    n = len(ids)
+    out = dict(id=np.array(ids, dtype=np.int64), feature=np.full(n, -1, dtype=np.int32), bin=np.full(n, -1, dtype=np.int32),
+               threshold=np.zeros(n), left=np.zeros(n, dtype=np.int32), right=np.zeros(n, dtype=np.int32),
+               prediction=np.zeros(n), probability=np.zeros(n), gain=np.zeros(n), impurity=np.zeros(n),
+               n=np.zeros(n, dtype=np.int64))
+    for nid, node in done.items():
+        i = at[nid]
+        for key in ("feature", "bin", "threshold", "gain", "impurity", "n", "prediction"):
+            out[key][i] = node[key]
+        out["probability"][i] = node["prediction"]          # (the member the prediction kernel writes out)
+        if node["feature"] >= 0:
+            out["left"][i], out["right"][i] = at[2 * nid], at[2 * nid + 1]
+    return out
 
 
 def _node_arrays(done: dict, K: int) -> dict:

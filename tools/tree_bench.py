@@ -31,6 +31,38 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
+def regression(pkg, torch, engine, bins, slots, n, d, MB, a):
+    """--regression: the target pass (range and targets over a caller's float64 labels), the moments pass, the
+    regression histogram at the root and over a 16-slot frontier, and the classifier's tree_hist at K = 2 on the
+    same binned rows and slots (the same table shape: 2 x 64 bits a bin); alternating, one process."""
+    from kmeans_bench import alternate
+    from project_bench import report
+    st, ctx, dev = engine.stream, engine.ctx, engine.dev
+    y = torch.randn(n, dtype=torch.float64, device=dev) * 3.0 - 1.0
+    t = engine.tree_targets(y)
+    rng = torch.zeros(3, dtype=torch.int64, device=dev)
+    mom = torch.zeros(16 * 4, dtype=torch.int64, device=dev)
+    hist = torch.zeros(1 + 16 * d * MB * 2, dtype=torch.int64, device=dev)
+
+    def targets():
+        ctx.tree_label_range_device(y.data_ptr(), rng.data_ptr(), st.cuda_stream)
+        ctx.tree_targets_device(y.data_ptr(), t.ymin, t.s, t.q.data_ptr(), st.cuda_stream)
+
+    calls = [("tree_targets (range + targets)", st, targets)]
+    for A in (1, 16):
+        calls += [(f"tree_moments A={A}", st, lambda A=A: ctx.tree_moments_device(
+                      t.q.data_ptr(), slots[A].data_ptr(), 0, A, mom.data_ptr(), st.cuda_stream)),
+                  (f"tree_hist_reg A={A}", st, lambda A=A: ctx.tree_histogram_reg_device(
+                      bins.bins.data_ptr(), t.q.data_ptr(), slots[A].data_ptr(), MB, 0, A, 0, hist.data_ptr() + 8, st.cuda_stream)),
+                  (f"tree_hist K=2 A={A}", st, lambda A=A: ctx.tree_histogram_device(
+                      bins.bins.data_ptr(), bins.labels.data_ptr(), slots[A].data_ptr(), 2, MB, 0, A, 0, hist.data_ptr() + 8,
+                      hist.data_ptr(), st.cuda_stream))]
+    ms = alternate(torch, calls, a.reps, a.warmup)
+    med = {name: report("c2", name, ms[name], {"rows": n, "features": d, "maxBins": MB}) for name in ms}
+    print(json.dumps({"shape": "c2", **{f"hist_reg_over_hist_K2_A{A}": round(med[f"tree_hist_reg A={A}"] / med[f"tree_hist K=2 A={A}"], 3)
+                                        for A in (1, 16)}}), flush=True)
+
+
 def main():
     from kmeans_bench import alternate
     from project_bench import report
@@ -39,6 +71,8 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--regression", action="store_true",
+                    help="time the regression passes beside the classifier's tree_hist at K = 2 on the same binned rows")
     a = ap.parse_args()
     if a.reps < 20:
         ap.error("--reps must be at least 20")
@@ -62,6 +96,8 @@ def main():
     print(f"rows ready: {n} x {d}; bins per feature {int(nbins.min())} .. {int(nbins.max())}", file=sys.stderr, flush=True)
 
     slots = {A: (torch.arange(n, device=dev, dtype=torch.int32) % A).contiguous() for A in (1, 2, 4, 8, 16, 32, 64)}
+    if a.regression:
+        return regression(pkg, torch, engine, bins, slots, n, d, MB, a)
     hist = torch.zeros(1 + 64 * d * MB * K, dtype=torch.int64, device=dev)
     rec = torch.zeros(64 * (6 + 2 * K), dtype=torch.float64, device=dev)
     w = torch.randn(d, dtype=torch.float64, device=dev) / d ** 0.5
